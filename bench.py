@@ -17,6 +17,9 @@ a bounded sample; N=1 only), and - N=1 only, bounded to about a minute - `extra.
 metric ("approx + exact, batch 512/4096", FetchArm B=8192), each with ms, rate, flow rows/s and its own fraction of the
 FP32-MFMA roofline.
 
+`--dump-outputs DIR`: after the timed steps, rank 0 writes the solutions the last timed step returned (all ranks' rows when N > 1) to
+DIR/solutions.npy in float32; every input is seeded, so two builds run with the same arguments can be compared output for output.
+
 `--dist-dry-run` (tests only): runs this file's process-group / step / fence / gather / max-over-ranks logic under gloo
 on CPU tensors with a stand-in row-wise function in place of the engine; the line it prints carries "dry_run": true and
 no throughput claim.
@@ -70,7 +73,34 @@ def parse():
                    help="do not measure roofline.traffic in this run (default at N=1: two rocprofv3 --pmc passes - FETCH_SIZE, WRITE_SIZE - "
                         "over a 4-step sub-run of the headline workload, ~10 s; the committed PMC summary is reported beside it and is the "
                         "fallback when rocprofv3 is not usable)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32; rank 0: "
+                        "the solutions, all ranks' rows when N > 1; above 64 MB a fixed seeded sample of rows, see dump_outputs)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each [rows x ...] array as out_dir/<name>.npy in float32.  An array above DUMP_LIMIT_BYTES (shared between the arrays) is
+    replaced by a fixed sample of its rows - numpy default_rng(0), sorted - so that two builds given the same arguments write the same
+    rows.  Returns {name: rows written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        row_bytes = max(a[:1].nbytes, 1)
+        if a.nbytes > budget:
+            keep = budget // row_bytes
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = int(a.shape[0])
+    return written
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -752,6 +782,12 @@ def main():
                          "per-layer kernels' weight image (+ 201 MB, ~3 ms) is built only by the first <= 512-row chunk that takes that path"}
     elapsed, sol = timed_steps(stepper, args.steps, args.warmup)
     assert bool(torch.isfinite(sol).all())
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's result as its caller holds it: this rank's solutions, or every rank's rows once gathered (N > 1)
+        last = stepper.last_gathered() if use_dist else sol
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"solutions": last.cpu().numpy()})
     rccl = None
     if use_dist:
         assert torch.equal(stepper.last_gathered()[rank * B : (rank + 1) * B], sol)  # own shard sits at its rank offset
@@ -933,6 +969,8 @@ def main():
     }
     if rccl is not None:
         out["rccl"] = rccl
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "rows": dumped}
     if TEST_BACKEND:
         out["test_backend"] = f"{TEST_BACKEND}: all {world} ranks share cuda:0 - a test of the N>1 code path, NOT a measurement"
         out["metric"] = "TEST RUN (ranks share one GPU): no throughput claim"
@@ -968,6 +1006,8 @@ def dry_run(args, world, rank, use_dist):
     latent = torch.randn(B, 7, generator=g)
     stepper = ShardedStepper(lambda: torch.tanh(poses) + 0.5 * latent, world, rank, B, 7, "cpu", use_dist)
     elapsed, sol = timed_steps(stepper, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"solutions": (stepper.last_gathered() if use_dist else sol).numpy()})
     ok = True
     if use_dist:
         full = stepper.last_gathered()

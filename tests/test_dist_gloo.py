@@ -101,6 +101,59 @@ def test_bench_dry_run_under_torch_distributed_run(extra, world):
     assert 0 < rc["rank_elapsed_ms_min"] <= rc["rank_elapsed_ms_max"]
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step_under_gloo(tmp_path):
+    """--dump-outputs on the dry run at world size 2: rank 0 writes what the last timed step handed its caller - every rank's rows, gathered
+    in rank order - as float32 .npy, and a second run with the same arguments writes the same bits."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    world, B = 2, 257
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+               "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
+               "--batch", str(B), "--dist-dry-run", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root,
+                           env=dict(os.environ, OMP_NUM_THREADS="1"))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["gathered_ok"] is True
+        assert sorted(os.listdir(d)) == ["solutions.npy"]
+        dumps.append(np.load(d / "solutions.npy"))
+    want = []
+    for rank in range(world):  # the dry run's stand-in compute on each rank's seeded inputs
+        g = torch.Generator().manual_seed(rank)
+        p, l = torch.randn(B, 7, generator=g), torch.randn(B, 7, generator=g)
+        want.append((torch.tanh(p) + 0.5 * l).numpy())
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (world * B, 7)
+    np.testing.assert_array_equal(dumps[0], np.concatenate(want))
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+
+
+def test_bench_dump_outputs_samples_a_fixed_set_of_rows_above_the_limit(tmp_path, monkeypatch):
+    """An output above the size limit is replaced by the same sorted, seeded sample of its rows on every call; below it, written whole."""
+    import numpy as np
+
+    import bench
+
+    a = np.arange(1000 * 7, dtype=np.float64).reshape(1000, 7)
+    assert bench.dump_outputs(str(tmp_path / "whole"), {"solutions": a}) == {"solutions": 1000}
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "solutions.npy"), a.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * 7 * 4)
+    assert bench.dump_outputs(str(tmp_path / "s1"), {"solutions": a}) == {"solutions": 100}
+    bench.dump_outputs(str(tmp_path / "s2"), {"solutions": a})
+    s1, s2 = np.load(tmp_path / "s1" / "solutions.npy"), np.load(tmp_path / "s2" / "solutions.npy")
+    assert s1.dtype == np.float32 and s1.nbytes <= bench.DUMP_LIMIT_BYTES
+    np.testing.assert_array_equal(s1, s2)
+    rows = (s1[:, 0] / 7).astype(int)
+    assert len(set(rows)) == 100 and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(s1, a[rows].astype(np.float32))
+
+
 def test_bench_refuses_more_ranks_than_visible_gpus_with_a_message_naming_the_variable():
     """LOCAL_RANK beyond the visible GPUs (a launch with --nproc-per-node above HIP_VISIBLE_DEVICES) must fail with a message that says so,
     not with a HIP error from set_device; and the NUMA-affinity record never raises, whatever sysfs offers."""

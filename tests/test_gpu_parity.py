@@ -2361,6 +2361,38 @@ def test_bench_two_ranks_on_one_gpu():
     assert "cpu_baseline" not in out and "cells" not in out["extra"]  # rank-0-at-N=1-only legs stay out of an N>1 line
 
 
+def test_bench_dump_outputs_is_the_timed_path_result(tmp_path):
+    """bench.py --dump-outputs on the headline workload: the file holds the last timed step's [4096 x 7] solutions, a second run with the same
+    arguments writes the same bits, and the rows are the oracle's on the bench's own seeded inputs (weights seed 0, poses = FK(q ~
+    default_rng(0)), latents manual_seed(1))."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cells", "--no-split-extra",
+               "--no-cpu-baseline", "--no-live-pmc", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 3 and out["dumped_outputs"]["rows"] == {"solutions": 4096}
+        dumps.append(np.load(d / "solutions.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (4096, 7)
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+    from ikflow_amd.robots import get_robot
+
+    robot, _, lay, sd = panda_model()
+    prod = get_robot("panda")
+    q = torch.tensor(prod.sample_joint_angles(4096, 0.004363323129985824, np.random.default_rng(0)), device=DEV)
+    poses = prod.forward_kinematics(q).cpu()
+    lat = latents(4096, lay.dim, 1)
+    ref = fo.generate_ik_solutions_torch(sd, lay, robot, poses, lat).numpy()
+    assert np.abs(dumps[0] - ref).max() <= 1e-5
+
+
 def test_repeated_interleaved_calls_are_bit_identical():
     """tools/determinism_soak.py, short form: the same call repeated while other batch sizes run in between (the engine's buffers are
     shared between sizes) returns identical bits - approximate IK on every tile path in both precisions, and exact IK."""
