@@ -73,13 +73,16 @@ __device__ __forceinline__ void ro_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// value of new-state element d of row `row` after the pending coupling of subnet `sm` (or the plain state when sm == null)
+// value of new-state element d of row `row` after the pending coupling of subnet `sm` (or the plain state when sm == null).
+// FWD (k_flow_rowowner_fwd): the coupling runs forward, y = exp(s) x + t, and the permutation of the table sits on the subnet-1 entries
+// (PermuteRandom of the NEXT block, see rowowner_fwd_table); ld (nullable) accumulates the clamped s of the elements this thread rewrites.
+template <bool FWD = false>
 __device__ __forceinline__ float ro_new_state(const float* __restrict__ xs_old, const float* __restrict__ red, const float* __restrict__ sm,
-                                              int row, int d, int L1, float clamp) {
+                                              int row, int d, int L1, float clamp, float* ld = nullptr) {
   if (sm == nullptr) return xs_old[row * 16 + d];
   const int* smi = reinterpret_cast<const int*>(sm);
   const int which = smi[32], nl = smi[35];
-  const int src = which == 2 ? smi[16 + d] : d;
+  const int src = which == (FWD ? 1 : 2) ? smi[16 + d] : d;
   const int off = which == 1 ? L1 : 0;
   float v = xs_old[row * 16 + src];
   if (src >= off && src < off + nl) {
@@ -91,15 +94,33 @@ __device__ __forceinline__ float ro_new_state(const float* __restrict__ xs_old, 
       tt += red[w * (RO_ROWS * RO_RS) + row * RO_RS + nl + j];
     }
     const float s_cl = clamp * (0.636f * atanf(s));
-    v = (v - tt) * expf(-s_cl);
+    if constexpr (FWD) {
+      v = expf(s_cl) * v + tt;
+      if (ld != nullptr) *ld += s_cl;
+    } else {
+      v = (v - tt) * expf(-s_cl);
+    }
   }
   return v;
 }
 
+// FWD: byte offset in the stream of the group at consumption position `lin` (wave offset included).  The forward pass executes the
+// subnets in the reverse of the stream's order (block 0 first, subnet 2 before subnet 1) and each subnet's groups in stream order, so
+// every group keeps its ring slot.  The ring's lead past the last subnet re-reads stream subnet 0 (never consumed; always in bounds).
+__device__ __forceinline__ unsigned ro_fwd_offset(unsigned lin, int n_sub) {
+  const unsigned i = lin / RO_GROUP_BYTES, sub = i / RO_SUB_GROUPS, g = i - sub * RO_SUB_GROUPS;
+  const unsigned ps = sub < (unsigned)n_sub ? (unsigned)n_sub - 1u - sub : 0u;
+  return (ps * RO_SUB_GROUPS + g) * RO_GROUP_BYTES + lin % RO_GROUP_BYTES;
+}
+
 #define RO_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-template <int NBUF>
-__global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
+// The body of both directions.  FWD = false: the inverse pass (k_flow_rowowner).  FWD = true: the forward (training-direction) pass
+// (k_flow_rowowner_fwd, ikflow/model.py:300-354): rows of x -> FixedLinearTransform (x.mm(M) + b; logit on sigmoid graphs) ->
+// PermuteRandom(0) -> per block: subnet 2, subnet 1, PermuteRandom of the next block -> z, plus the per-row log-determinant.  Same LDS map,
+// same stream and ring; only the schedule (ro_fwd_offset), the coupling (ro_new_state<true>), the head and the tail differ.
+template <int NBUF, bool FWD>
+__device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
   static_assert(RO_SUB_GROUPS % NBUF == 0 && RO_KG % NBUF == 0, "ring length must divide the subnet's group count");
   constexpr int PF = NBUF - 1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -126,7 +147,7 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
   ro_f4 wb[NBUF][RO_NCB];
 #define RO_ISSUE(slot)                                                                                                             \
   {                                                                                                                                \
-    const unsigned so_ = __builtin_amdgcn_readfirstlane(g_issue);                                                                  \
+    const unsigned so_ = __builtin_amdgcn_readfirstlane(FWD ? ro_fwd_offset(g_issue, a.n_sub) : g_issue);                          \
     _Pragma("unroll") for (int cb_ = 0; cb_ < RO_NCB; ++cb_)                                                                       \
         wb[slot][cb_] = __builtin_bit_cast(ro_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + cb_ * 1024, so_, 0));           \
     g_issue += RO_GROUP_BYTES;                                                                                                     \
@@ -135,11 +156,28 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
   for (int s = 0; s < PF; ++s) RO_ISSUE(s)
 
   // ---- rows: state, conditional, per-subnet small parameters -> LDS
+  float ld = 0.f;   // (FWD, threads 0..255) this thread's share of its row's log-determinant
   if (t < 256) {
     const int row = t >> 4, d = t & 15;
     int gr = m0 + row;
     gr = gr < a.M ? gr : a.M - 1;
-    xs[row * 16 + d] = d < a.D ? a.x0[(size_t)gr * a.D + d] : 0.f;
+    if constexpr (FWD) {
+      // FixedLinearTransform forward, element perm0[d] (PermuteRandom(0) applied on the way into LDS); sigmoid graphs: InvertibleSigmoidFlipped
+      // forward = logit, whose log-det term is -log(v (1 - v)) (ikflow/model.py:136-146)
+      float v = 0.f;
+      if (d < a.D) {
+        const int src = f.perm0[d];
+        for (int k = 0; k < a.D; ++k) v = fmaf(a.x0[(size_t)gr * a.D + k], f.M[k * a.D + src], v);
+        v += a.b_lin[src];
+        if (a.sigmoid) {
+          ld = -(logf(v) + log1pf(-v));
+          v = logf(v / (1.0f - v));
+        }
+      }
+      xs[row * 16 + d] = v;
+    } else {
+      xs[row * 16 + d] = d < a.D ? a.x0[(size_t)gr * a.D + d] : 0.f;
+    }
   } else if (t < 256 + 128) {
     const int row = (t - 256) >> 3, k = t & 7;
     int gr = m0 + row;
@@ -157,7 +195,7 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
   auto advance = [&](const float* pend_sm, const float* nxt_sm, const float* xs_old, float* xs_new) {
     if (t < 256) {
       const int row = t >> 4, d = t & 15;
-      if (d < a.D) xs_new[row * 16 + d] = ro_new_state(xs_old, red, pend_sm, row, d, a.L1, a.clamp);
+      if (d < a.D) xs_new[row * 16 + d] = ro_new_state<FWD>(xs_old, red, pend_sm, row, d, a.L1, a.clamp, FWD ? &ld : nullptr);
     } else if (nxt_sm != nullptr) {
       const int row = (t - 256) >> 4, k = t & 15;
       const int* ni = reinterpret_cast<const int*>(nxt_sm);
@@ -167,7 +205,7 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
       if (what >= 0) v = cond[row * 8 + what];
       else if (what == -1) v = 1.0f;
       else if (what == -100) v = cond[row * 8 + 7];
-      else if (what > -100) v = ro_new_state(xs_old, red, pend_sm, row, x_off + (-2 - what), a.L1, a.clamp);
+      else if (what > -100) v = ro_new_state<FWD>(xs_old, red, pend_sm, row, x_off + (-2 - what), a.L1, a.clamp);
       us[row * RO_US + k] = v;
     }
   };
@@ -273,8 +311,21 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
     RO_PHASE(5)
   }
   RO_STAMP(33)
-  // ---- FixedLinearTransform rev: (x - b).mm(M_inv); [:, :ndof]; clamp_to_joint_limits
-  if (t < 256) {
+  if constexpr (FWD) {
+    // ---- z rows; log-det = logDetM + the row's 16 shares, summed in a fixed butterfly order (a row's result does not depend on its place)
+    if (t < 256) {
+      const int row = t >> 4, d = t & 15;
+      const bool live = m0 + row < a.M;
+      if (f.z_out != nullptr && live && d < a.D) f.z_out[(size_t)(m0 + row) * a.D + d] = xs[256 * xcur + row * 16 + d];
+      float s = ld;
+      s += __shfl_xor(s, 8, 16);
+      s += __shfl_xor(s, 4, 16);
+      s += __shfl_xor(s, 2, 16);
+      s += __shfl_xor(s, 1, 16);
+      if (f.ld_out != nullptr && live && d == 0) f.ld_out[m0 + row] = f.log_det0 + s;
+    }
+  } else if (t < 256) {
+    // ---- FixedLinearTransform rev: (x - b).mm(M_inv); [:, :ndof]; clamp_to_joint_limits
     const int row = t >> 4, j = t & 15;
     if (j < a.ndof && m0 + row < a.M) {
       const float* x = xs + 256 * xcur + row * 16;
@@ -294,6 +345,17 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
     a.trace[(size_t)blockIdx.x * 64 + 35] = ro_t0_wall;
   }
 #undef RO_STAMP
+}
+
+template <int NBUF>
+__global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
+  ro_flow_body<NBUF, false>(a, RoFwd{});
+}
+// The forward pass (ikf_flow_forward): a.sub = the forward-order table (rowowner_fwd_table), a.x0 = joint rows [M][D], a.b_lin = b.
+// Small batches take it too (under-occupied); there is no cluster form of it.
+template <int NBUF>
+__global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner_fwd(RoArgs a, RoFwd f) {
+  ro_flow_body<NBUF, true>(a, f);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -963,6 +1025,15 @@ hipError_t launch_flow_rowowner(const RoArgs& a, int nbuf, hipStream_t s) {
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_flow_rowowner<4>, dim3(grid), dim3(RO_WAVES * 64), RO_LDS_BYTES, s, a);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_flow_rowowner_fwd(const RoArgs& a, const RoFwd& f, hipStream_t s) {
+  static bool done[64] = {};
+  const unsigned grid = (unsigned)((a.M + RO_ROWS - 1) / RO_ROWS);
+  hipError_t e = ensure_dynamic_lds(k_flow_rowowner_fwd<4>, RO_LDS_BYTES, done);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_flow_rowowner_fwd<4>, dim3(grid), dim3(RO_WAVES * 64), RO_LDS_BYTES, s, a, f);
   return hipGetLastError();
 }
 

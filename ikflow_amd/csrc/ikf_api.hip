@@ -6,6 +6,8 @@
 #include <cstring>
 #include <string>
 #include <chrono>
+#include <cmath>
+#include <utility>
 #include <unordered_map>
 #include <vector>
 
@@ -150,6 +152,11 @@ struct ikf_model {
   std::vector<SubnetWeights> subnets;  // [2*block + (which-1)]
   int* d_perm_inv = nullptr;           // [nb_nodes][D]
   float* d_Minv = nullptr;             // [D][D]
+  // forward (training-direction) pass, ikf_flow_forward
+  float* d_M = nullptr;                // [D][D] FixedLinearTransform forward matrix (module_list.0.M, or the fp64 inverse of M_inv)
+  int* d_perm = nullptr;               // [nb_nodes][D] PermuteRandom forward: perm[perm_inv[k]] = k
+  float log_det_M = 0.f;               // logDetM = log|det M|, fp64 at load
+  RoSubnet* d_ro_sub_fwd = nullptr;    // the row-owner table in forward execution order (rowowner_fwd_table)
   float* d_blin = nullptr;             // [D]
   Chain* d_chain = nullptr;            // robot chain + limits
   CollisionModel* d_collision = nullptr;  // capsules + pairs (ikf_set_collision_model), or null
@@ -361,6 +368,7 @@ extern "C" void ikf_destroy(ikf_model* m) {
   if (m->wfrag_arena) (void)hipFree(m->wfrag_arena);
   if (m->ro_stream) (void)hipFree(m->ro_stream);
   if (m->d_ro_sub) (void)hipFree(m->d_ro_sub);
+  if (m->d_ro_sub_fwd) (void)hipFree(m->d_ro_sub_fwd);
   if (m->cl_xbuf) (void)hipFree(m->cl_xbuf);
   if (m->cl_sync) (void)hipFree(m->cl_sync);
   if (m->cl_xbuf_t) (void)hipFree(m->cl_xbuf_t);
@@ -368,6 +376,8 @@ extern "C" void ikf_destroy(ikf_model* m) {
   if (m->h_cl_give_up) (void)hipHostFree(m->h_cl_give_up);
   if (m->d_perm_inv) (void)hipFree(m->d_perm_inv);
   if (m->d_Minv) (void)hipFree(m->d_Minv);
+  if (m->d_M) (void)hipFree(m->d_M);
+  if (m->d_perm) (void)hipFree(m->d_perm);
   if (m->d_blin) (void)hipFree(m->d_blin);
   if (m->d_chain) (void)hipFree(m->d_chain);
   if (m->d_collision) (void)hipFree(m->d_collision);
@@ -506,11 +516,26 @@ static ikf_status ensure_cluster_scratch(ikf_model* m, long long rows);
 static void drop_rowowner_stream(ikf_model* m) {
   if (m->ro_stream) { (void)hipFree(m->ro_stream); m->ro_stream = nullptr; }
   if (m->d_ro_sub) { (void)hipFree(m->d_ro_sub); m->d_ro_sub = nullptr; }
+  if (m->d_ro_sub_fwd) { (void)hipFree(m->d_ro_sub_fwd); m->d_ro_sub_fwd = nullptr; }
+}
+// The forward pass walks the same stream with the subnets in reverse order (k_flow_rowowner_fwd, ro_fwd_offset); its table lists them in
+// forward execution order (block 0 .. NB-1, subnet 2 then subnet 1).  PermuteRandom forward of block b + 1 rides on block b's subnet-1 entry
+// (identity on the last block); block 0's goes to the kernel as RoFwd::perm0.
+static std::vector<RoSubnet> rowowner_fwd_table(const std::vector<RoSubnet>& inv, int NB, int D, const std::vector<int>& perm_fwd) {
+  const int n_sub = 2 * NB;
+  std::vector<RoSubnet> tab(n_sub);
+  for (int s = 0; s < n_sub; ++s) {
+    RoSubnet r = inv[n_sub - 1 - s];
+    const int b = s / 2;
+    for (int k = 0; k < 16; ++k) r.perm_inv[k] = (r.which == 1 && b + 1 < NB && k < D) ? perm_fwd[(size_t)(b + 1) * D + k] : k;
+    tab[s] = r;
+  }
+  return tab;
 }
 // Nothing here is needed by the per-layer kernels: whatever fails (the second 203 MB, the census launch, the exchange buffers) leaves the
 // handle WITHOUT the resident-row forms - rowowner_allowed / cluster_allowed test ro_stream - and ikf_load_weights still succeeds; the
 // reason is kept for ikf_last_error.
-static hipError_t build_rowowner_stream_hip(ikf_model* m, const std::vector<int>& perm_host) {
+static hipError_t build_rowowner_stream_hip(ikf_model* m, const std::vector<int>& perm_host, const std::vector<int>& perm_fwd) {
   const FlowDims& d = m->dims;
   const int NB = m->desc.nb_nodes, n_sub = 2 * NB;
   const size_t floats = rowowner_stream_floats(n_sub);
@@ -530,6 +555,9 @@ static hipError_t build_rowowner_stream_hip(ikf_model* m, const std::vector<int>
     r.which = which; r.n_x = w.n_x; r.x_off = which == 1 ? 0 : d.L1; r.n_half = w.n_out / 2;
   }
   if ((e = hipMemcpy(m->d_ro_sub, tab.data(), sizeof(RoSubnet) * n_sub, hipMemcpyHostToDevice)) != hipSuccess) return e;
+  const std::vector<RoSubnet> fwd = rowowner_fwd_table(tab, NB, d.D, perm_fwd);
+  if ((e = hipMalloc(&m->d_ro_sub_fwd, sizeof(RoSubnet) * n_sub)) != hipSuccess) return e;
+  if ((e = hipMemcpy(m->d_ro_sub_fwd, fwd.data(), sizeof(RoSubnet) * n_sub, hipMemcpyHostToDevice)) != hipSuccess) return e;
   if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
   // the XCD-local hand-over of the cluster form (G = 4 / 8 / 16) needs workgroups b and b + 8 k of a grid on one XCD: asked of the device once
   // (and checked again by every such launch among its own members)
@@ -539,13 +567,13 @@ static hipError_t build_rowowner_stream_hip(ikf_model* m, const std::vector<int>
   if (!grouped) m->cl_local = 0;
   return hipSuccess;
 }
-static ikf_status build_rowowner_stream(ikf_model* m, const std::vector<int>& perm_host) {
+static ikf_status build_rowowner_stream(ikf_model* m, const std::vector<int>& perm_host, const std::vector<int>& perm_fwd) {
   const FlowDims& d = m->dims;
   const int n_sub = 2 * m->desc.nb_nodes;
   drop_rowowner_stream(m);
   if (!rowowner_shape_ok(d, n_sub) || d.slope < 0.f || d.slope > 1.f) return IKF_OK;
   if (rowowner_stream_floats(n_sub) * 4 >= (size_t)1 << 32) return IKF_OK;  // (one 32-bit buffer descriptor)
-  hipError_t e = build_rowowner_stream_hip(m, perm_host);
+  hipError_t e = build_rowowner_stream_hip(m, perm_host, perm_fwd);
   // the cluster form's exchange buffers have one size (8 MB + 1.2 MB): reserved here, so that no call ever allocates for them
   if (e == hipSuccess && ensure_cluster_scratch(m, 1) != IKF_OK) e = hipErrorOutOfMemory;
   if (e != hipSuccess) {
@@ -667,16 +695,70 @@ extern "C" ikf_status ikf_load_weights(ikf_model* m, const ikf_tensor* tensors, 
     memcpy(blin.data(), tb->h_data, sizeof(float) * D);
   }
 
+  // forward pass: M (the file's, or the fp64 inverse of M_inv), logDetM = log|det M| in fp64, PermuteRandom forward tables
+  std::vector<double> M64((size_t)D * D), Minv64((size_t)D * D);
+  for (int k = 0; k < D * D; ++k) Minv64[k] = static_cast<const float*>(tM->h_data)[k];
+  const ikf_tensor* tMf = find_tensor(idx, "module_list.0.M");
+  if (tMf) {
+    int64_t numel = 1;
+    for (int k = 0; k < tMf->ndim; ++k) numel *= tMf->shape[k];
+    if (tMf->dtype != 0 || !tMf->h_data || numel != (int64_t)D * D) return fail(IKF_ERR_MISSING_TENSOR, "size mismatch for module_list.0.M");
+    for (int k = 0; k < D * D; ++k) M64[k] = static_cast<const float*>(tMf->h_data)[k];
+  }
+  double log_det = 0.0;
+  {
+    // LU with partial pivoting of M (or of M_inv: log|det M| = -log|det M_inv|), fp64; M_inv is inverted on the side when M is absent
+    std::vector<double> A = tMf ? M64 : Minv64;
+    std::vector<double> X((size_t)D * D, 0.0);
+    for (int k = 0; k < D; ++k) X[(size_t)k * D + k] = 1.0;
+    for (int c = 0; c < D; ++c) {
+      int p = c;
+      for (int r = c + 1; r < D; ++r)
+        if (fabs(A[(size_t)r * D + c]) > fabs(A[(size_t)p * D + c])) p = r;
+      if (A[(size_t)p * D + c] == 0.0) return fail(IKF_ERR_BAD_ARGUMENT, "ikf_load_weights: the FixedLinearTransform matrix is singular");
+      if (p != c)
+        for (int k = 0; k < D; ++k) {
+          std::swap(A[(size_t)p * D + k], A[(size_t)c * D + k]);
+          std::swap(X[(size_t)p * D + k], X[(size_t)c * D + k]);
+        }
+      log_det += log(fabs(A[(size_t)c * D + c]));
+      for (int r = 0; r < D; ++r) {
+        if (r == c) continue;
+        const double f = A[(size_t)r * D + c] / A[(size_t)c * D + c];
+        if (f == 0.0) continue;
+        for (int k = 0; k < D; ++k) {
+          A[(size_t)r * D + k] -= f * A[(size_t)c * D + k];
+          X[(size_t)r * D + k] -= f * X[(size_t)c * D + k];
+        }
+      }
+    }
+    if (!tMf) {
+      log_det = -log_det;
+      for (int r = 0; r < D; ++r)
+        for (int k = 0; k < D; ++k) M64[(size_t)r * D + k] = X[(size_t)r * D + k] / A[(size_t)r * D + r];
+    }
+  }
+  std::vector<float> M32((size_t)D * D);
+  for (int k = 0; k < D * D; ++k) M32[k] = (float)M64[k];
+  std::vector<int> perm_fwd((size_t)NB * D);
+  for (int b = 0; b < NB; ++b)
+    for (int k = 0; k < D; ++k) perm_fwd[(size_t)b * D + perm_host[(size_t)b * D + k]] = k;
+
   // upload
   if (m->arena) { (void)hipFree(m->arena); m->arena = nullptr; }
   if (!m->d_perm_inv) IKF_HIP(hipMalloc(&m->d_perm_inv, sizeof(int) * (size_t)NB * D));
   if (!m->d_Minv) IKF_HIP(hipMalloc(&m->d_Minv, sizeof(float) * D * D));
+  if (!m->d_M) IKF_HIP(hipMalloc(&m->d_M, sizeof(float) * D * D));
+  if (!m->d_perm) IKF_HIP(hipMalloc(&m->d_perm, sizeof(int) * (size_t)NB * D));
   if (!m->d_blin) IKF_HIP(hipMalloc(&m->d_blin, sizeof(float) * D));
   IKF_HIP(hipMalloc(&m->arena, sizeof(float) * total));
   m->arena_floats = total;
   IKF_HIP(hipMemcpy(m->arena, host.data(), sizeof(float) * total, hipMemcpyHostToDevice));
   IKF_HIP(hipMemcpy(m->d_perm_inv, perm_host.data(), sizeof(int) * (size_t)NB * D, hipMemcpyHostToDevice));
   IKF_HIP(hipMemcpy(m->d_Minv, tM->h_data, sizeof(float) * D * D, hipMemcpyHostToDevice));
+  IKF_HIP(hipMemcpy(m->d_M, M32.data(), sizeof(float) * D * D, hipMemcpyHostToDevice));
+  IKF_HIP(hipMemcpy(m->d_perm, perm_fwd.data(), sizeof(int) * (size_t)NB * D, hipMemcpyHostToDevice));
+  m->log_det_M = (float)log_det;
   IKF_HIP(hipMemcpy(m->d_blin, blin.data(), sizeof(float) * D, hipMemcpyHostToDevice));
   for (int si = 0; si < 2 * NB; ++si) {
     SubnetWeights& s = subs[si];
@@ -701,7 +783,7 @@ extern "C" ikf_status ikf_load_weights(ikf_model* m, const ikf_tensor* tensors, 
   m->loaded = false;
   m->chain_tab_valid = false;  // (the chain's argument table points into the weight arenas)
   drop_frag_weights(m);        // (rebuilt from the new arena by the first chunk that needs them, or by ikf_reserve)
-  ikf_status fst = build_rowowner_stream(m, perm_host);
+  ikf_status fst = build_rowowner_stream(m, perm_host, perm_fwd);
   if (fst != IKF_OK) return fst;
   m->loaded = true;
   m->cl_pause = m->cl_backoff = 0;
@@ -1601,6 +1683,92 @@ extern "C" ikf_status ikf_generate_approx(ikf_model* m, const float* d_poses, in
   StreamScope scope(m, s);
   IKF_HIP(scope.enter());
   st = run_flow_guarded(m, ps, d_latent, n, clamp_to_limits, d_q_out, s);
+  if (st != IKF_OK) return st;
+  IKF_HIP(scope.leave());
+  return IKF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// forward (training-direction) pass: nn_model(x, c=cond, jac=True) of ikflow/training/lt_model.py:156
+// ---------------------------------------------------------------------------------------------------------------
+// The released width (1024, 3 hidden layers): one k_flow_rowowner_fwd launch for any batch size (no cluster form).  Every other shape: the
+// per-layer kernels, chunked like the inverse pass (state in xbuf, running log-det in xbuf2).
+static ikf_status run_forward_rowowner(ikf_model* m, const PoseSource& ps, const float* d_x, long long rows, float* d_z, float* d_ld,
+                                       hipStream_t s) {
+  const long long kMaxLaunchRows = 1LL << 24;
+  const FlowDims& d = m->dims;
+  for (long long r0 = 0; r0 < rows; r0 += kMaxLaunchRows) {
+    const long long nr = rows - r0 < kMaxLaunchRows ? rows - r0 : kMaxLaunchRows;
+    RoArgs a = rowowner_args(m, ps, d_x, r0, nr, 0, nullptr);
+    a.sub = m->d_ro_sub_fwd;
+    a.M_inv = nullptr; a.q_out = nullptr;
+    RoFwd f{};
+    f.M = m->d_M;
+    f.perm0 = m->d_perm;
+    f.log_det0 = m->log_det_M;
+    f.z_out = d_z ? d_z + (size_t)r0 * d.D : nullptr;
+    f.ld_out = d_ld ? d_ld + r0 : nullptr;
+    IKF_HIP(launch_flow_rowowner_fwd(a, f, s));
+  }
+  return IKF_OK;
+}
+static ikf_status run_forward_chunk_per_layer(ikf_model* m, const PoseSource& ps, const float* d_x, long long r0, long long nr, float* d_z,
+                                              float* d_ld, hipStream_t s) {
+  const FlowDims& d = m->dims;
+  const int NB = m->desc.nb_nodes;
+  const int variant = pick_variant(m, nr);
+  FwdEntryArgs ea{};
+  ea.x = d_x + (size_t)r0 * d.D;
+  ea.M = m->d_M; ea.b_lin = m->d_blin; ea.perm0 = m->d_perm; ea.log_det0 = m->log_det_M;
+  ea.D = d.D; ea.sigmoid = m->desc.sigmoid_on_output ? 1 : 0;
+  ea.state = m->xbuf; ea.ld = m->xbuf2;
+  IKF_HIP(launch_fwd_entry(ea, nr, s));
+  for (int b = 0; b < NB; ++b) {
+    for (int which = 2; which >= 1; --which) {
+      const SubnetWeights& w = m->subnets[2 * b + which - 1];
+      IKF_HIP(launch_first_layer(w, d, m->xbuf, which == 1 ? 0 : d.L1, ps, r0, nr, m->hA, s));
+      float* cur = m->hA;
+      float* nxt = m->hB;
+      for (int l = 0; l < d.n_hidden - 1; ++l) {
+        IKF_HIP(launch_gemm_lrelu(variant, cur, w.w_mid[l], w.b_mid[l], nxt, nr, d.width, d.width, d.slope, s));
+        float* tmp = cur; cur = nxt; nxt = tmp;
+      }
+      FwdCouplingArgs ca{};
+      ca.state = m->xbuf;
+      ca.perm_next = (which == 1 && b + 1 < NB) ? m->d_perm + (size_t)(b + 1) * d.D : nullptr;
+      ca.ld = m->xbuf2;
+      ca.which = which;
+      ca.is_final = (b == NB - 1 && which == 1) ? 1 : 0;
+      ca.z_out = d_z ? d_z + (size_t)r0 * d.D : nullptr;
+      ca.ld_out = d_ld ? d_ld + r0 : nullptr;
+      IKF_HIP(launch_last_layer_coupling_fwd(w, d, cur, ca, nr, s));
+    }
+  }
+  return IKF_OK;
+}
+
+extern "C" ikf_status ikf_flow_forward(ikf_model* m, const float* d_x, int64_t n, const float* d_poses, int pose_broadcast,
+                                       float softflow_scale, float* d_z_out, float* d_log_det_out, void* stream) {
+  ikf_status st = check_ready(m, "ikf_flow_forward");
+  if (st != IKF_OK) return st;
+  if (n < 0) return fail(IKF_ERR_BAD_ARGUMENT, "ikf_flow_forward: n must be >= 0");
+  if (n == 0) return IKF_OK;
+  if (!d_x || !d_poses) return fail(IKF_ERR_NULL_POINTER, "ikf_flow_forward: null device pointer");
+  if (!d_z_out && !d_log_det_out) return fail(IKF_ERR_NULL_POINTER, "ikf_flow_forward: d_z_out and d_log_det_out are both null");
+  IKF_ON_DEVICE(m)
+  PoseSource ps{d_poses, nullptr, pose_broadcast ? 1 : (long long)n, 7, softflow_scale};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  StreamScope scope(m, s);
+  IKF_HIP(scope.enter());
+  if (m->d_ro_sub_fwd != nullptr) {
+    st = run_forward_rowowner(m, ps, d_x, n, d_z_out, d_log_det_out, s);
+  } else {
+    st = ensure_scratch(m, n);
+    for (long long r0 = 0; st == IKF_OK && r0 < n; r0 += m->chunk_rows) {
+      const long long nr = n - r0 < m->chunk_rows ? n - r0 : m->chunk_rows;
+      st = run_forward_chunk_per_layer(m, ps, d_x, r0, nr, d_z_out, d_log_det_out, s);
+    }
+  }
   if (st != IKF_OK) return st;
   IKF_HIP(scope.leave());
   return IKF_OK;

@@ -77,6 +77,30 @@ hipError_t launch_last_layer_coupling(const SubnetWeights& w, const FlowDims& d,
 int gemm_variant_count();
 const char* gemm_kernel_name();
 
+// flow_forward.hip - the forward (training-direction) pass on the per-layer kernels (shapes without the row-owner launch)
+struct FwdEntryArgs {   // FixedLinearTransform forward (+ logit), PermuteRandom(0); ld[row] = logDetM (+ the sigmoid's term)
+  const float* x;       // [rows][D] joint rows (padded)
+  const float* M;       // [D][D]
+  const float* b_lin;   // [D]
+  const int* perm0;     // [D]
+  float log_det0;
+  int D, sigmoid;
+  float* state;         // [rows][D]
+  float* ld;            // [rows]
+};
+hipError_t launch_fwd_entry(const FwdEntryArgs& a, long long rows, hipStream_t s);
+struct FwdCouplingArgs {
+  float* state;          // [rows][D], updated in place
+  const int* perm_next;  // [D] PermuteRandom forward of the next block (which == 1 of a block that has one), else null
+  float* ld;             // [rows] running log-det
+  int which;             // 2 (first in a block) or 1
+  int is_final;          // last subnet: write z_out / ld_out (each nullable)
+  float* z_out;
+  float* ld_out;
+};
+hipError_t launch_last_layer_coupling_fwd(const SubnetWeights& w, const FlowDims& d, const float* h_in, const FwdCouplingArgs& ca,
+                                          long long rows, hipStream_t s);
+
 // flow_fused.hip - the three-kernel-per-subnet form: the last Linear is reduced to per-tile partial sums in the epilogue
 // of the last hidden contraction, and the affine-coupling update runs at the head of the NEXT subnet's entry kernel.
 constexpr int IKF_PSTRIDE = 16;  // floats per row in one partial-sum slot
@@ -231,6 +255,14 @@ struct RoArgs {
   const unsigned* run_if;  // null, or a device word: the launch does nothing unless it is non-zero (the cluster form's repair launch)
 };
 
+struct RoFwd {             // k_flow_rowowner_fwd only: the forward pass's own inputs and outputs
+  const float* M;          // [D][D] FixedLinearTransform forward: v = x.mm(M) + b (b = RoArgs::b_lin)
+  const int* perm0;        // [16] PermuteRandom(seed=0) forward: state[d] = v[perm0[d]]
+  float log_det0;          // logDetM (fp64 at load, stored f32)
+  float* z_out;            // [M][D], or null
+  float* ld_out;           // [M], or null
+};
+
 struct RcArgs {            // cluster form (k_flow_cluster<G>): G workgroups per row tile split the hidden columns
   RoArgs ro;
   int n_rt;                // row tiles = ceil(M / 16); grid = n_rt * G workgroups, all resident
@@ -262,6 +294,8 @@ size_t rowowner_stream_floats(int n_sub);               // whole image incl. the
 bool rowowner_shape_ok(const FlowDims& d, int n_sub);
 hipError_t launch_rowowner_pack(const SubnetWeights& w, float* out, hipStream_t s);
 hipError_t launch_flow_rowowner(const RoArgs& a, int nbuf, hipStream_t s);
+// the forward (training-direction) pass in one launch (ikf_flow_forward): a.sub = the forward-order subnet table, a.x0 = joint rows
+hipError_t launch_flow_rowowner_fwd(const RoArgs& a, const RoFwd& f, hipStream_t s);
 const char* rowowner_kernel_name();
 
 // flow_split.hip - the hidden contraction on the f16 matrix cores with an error-compensated operand split:

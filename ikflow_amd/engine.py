@@ -226,6 +226,27 @@ class Engine:
             )
         return out
 
+    # -- forward (training-direction) pass ----------------------------------------------------------
+    def flow_forward(self, x: torch.Tensor, poses: torch.Tensor, softflow_scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """x [n x D] padded joint rows; poses [n x 7] or [7] (broadcast) -> (z [n x D], log_det [n]) (ikf_flow_forward)."""
+        x = self._on_device(x, "x")
+        poses = self._on_device(poses, "y")
+        n = x.shape[0]
+        assert x.ndim == 2 and x.shape[1] == self.layout.dim, f"x must be [n x {self.layout.dim}], got {tuple(x.shape)}"
+        broadcast = poses.numel() == 7
+        if not broadcast:
+            assert poses.ndim == 2 and poses.shape[1] == 7 and poses.shape[0] == n, f"{poses.shape[0]} != {n}"
+        z = torch.empty((n, self.layout.dim), dtype=torch.float32, device=self.device)
+        log_det = torch.empty((n,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(
+                self.lib.ikf_flow_forward(
+                    self._h, x.data_ptr(), n, poses.data_ptr(), 1 if broadcast else 0, float(softflow_scale),
+                    z.data_ptr(), log_det.data_ptr(), self._stream(),
+                )
+            )
+        return z, log_det
+
     # -- kinematics ----------------------------------------------------------------------------------
     def _q(self, q: torch.Tensor) -> torch.Tensor:
         q = self._on_device(q, "q")

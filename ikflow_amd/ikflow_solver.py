@@ -240,6 +240,56 @@ class IKFlowSolver:
             return solutions, valids
         return out
 
+    # -- log-likelihood (forward pass) ----------------------------------------------------------------------
+    def _forward_inputs(self, solutions: torch.Tensor, target_poses: torch.Tensor, pad: Optional[torch.Tensor]):
+        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
+        assert isinstance(solutions, torch.Tensor) and solutions.ndim == 2, "solutions must be [n x ndof]"
+        ndof, dim = self._robot.ndof, self._network_width
+        n = solutions.shape[0]
+        assert solutions.shape[1] == ndof, f"solutions must be [n x {ndof}], got {tuple(solutions.shape)}"
+        assert target_poses.numel() == 7 or (target_poses.ndim == 2 and target_poses.shape == (n, 7)), (
+            f"target_poses must be [7] or [{n} x 7], got {tuple(target_poses.shape)}")
+        if pad is None:
+            pad = torch.zeros((n, dim - ndof), dtype=torch.float32, device=solutions.device)
+        assert pad.shape == (n, dim - ndof), f"pad must be [{n} x {dim - ndof}], got {tuple(pad.shape)}"
+        x = torch.cat([solutions.to(torch.float32), pad.to(device=solutions.device, dtype=torch.float32)], 1)
+        return x, target_poses
+
+    def nn_forward(self, x: torch.Tensor, conditional: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The reference's ``nn_model(x, c=conditional, jac=True)`` (ikflow/training/lt_model.py:156): x [n x dim_tot] padded joint rows,
+        conditional [n x dim_cond] = [pose (7), softflow scale (softflow models)] -> (z [n x dim_tot], log|det J| [n]).  The engine takes
+        ONE softflow scale per call: a softflow column that varies across rows is refused."""
+        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
+        n = x.shape[0]
+        assert conditional.ndim == 2 and conditional.shape[0] == n and conditional.shape[1] in (7, 8), (
+            f"conditional must be [{n} x 7 or 8], got {tuple(conditional.shape)}")
+        scale = 0.0
+        if conditional.shape[1] == 8 and n > 0:
+            col = conditional[:, 7]
+            scale = float(col[0].item())
+            assert bool((col == col[0]).all().item()), "the softflow column must hold one value for every row"
+        poses = conditional[:, :7].contiguous()
+        return self.engine(x.device).flow_forward(x, poses, scale)
+
+    def log_prob(self, solutions: torch.Tensor, target_poses: torch.Tensor, pad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """log p(q | pose) under the flow, per row: -0.5 |z|^2 - 0.5 D log(2 pi) + log|det dz/dx|, D = dim_tot - the FULL conditional
+        log-density, Gaussian normaliser included (the reference's training loss drops it: see ``nll``).
+
+        solutions: [n x ndof] joint angles; target_poses: [n x 7] or a single pose [7].  The flow runs on [n x dim_tot] rows: the columns
+        beyond ndof come from ``pad`` ([n x (dim_tot - ndof)]) when given and are ZERO otherwise (the reference pads with 0.001 randn during
+        training; nothing random is drawn here).  Rows outside the joint limits are not refused: they give a defined but meaningless value
+        (NaN on sigmoid_on_output graphs)."""
+        x, poses = self._forward_inputs(solutions, target_poses, pad)
+        z, log_det = self.engine(x.device).flow_forward(x, poses)
+        return -0.5 * (z * z).sum(1) - 0.5 * z.shape[1] * float(np.log(2.0 * np.pi)) + log_det
+
+    def nll(self, solutions: torch.Tensor, target_poses: torch.Tensor, pad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The reference's per-row training loss term, literally: 0.5 |z|^2 - log|det J| (ikflow/training/lt_model.py:157-158; no Gaussian
+        normaliser, so the numbers compare with training logs).  Same arguments and padding rule as ``log_prob``."""
+        x, poses = self._forward_inputs(solutions, target_poses, pad)
+        z, log_det = self.engine(x.device).flow_forward(x, poses)
+        return 0.5 * (z * z).sum(1) - log_det
+
     # -- weights -------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict_filename: str):
         """Set the model's weights from a pickled state_dict (ikflow_solver.py:413-441) or a .npz with the same keys."""
