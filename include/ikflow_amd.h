@@ -123,7 +123,7 @@ ikf_status ikf_set_exact_upfront_rows(ikf_model* m, int64_t max_rows);
  * softflow_scale: the 8th conditional entry (always 0.0 at inference, :335-338). */
 ikf_status ikf_generate_approx(ikf_model* m, const float* d_poses, int pose_broadcast, const float* d_latent,
                                int64_t n, int clamp_to_limits, float softflow_scale, float* d_q_out, void* stream);
-/* GraphINN forward (ikflow/model.py:300-354): d_x [n x dim_tot], d_poses as above -> d_z_out [n x dim_tot], d_log_det_out [n], nullable */
+/* GraphINN forward (model.py:300-354): d_x [n x D], d_poses as above -> d_z_out [n x D], d_log_det_out [n], nullable; f32 in either precision */
 ikf_status ikf_flow_forward(ikf_model* m, const float* d_x, int64_t n, const float* d_poses, int pose_broadcast,
                             float softflow_scale, float* d_z_out, float* d_log_det_out, void* stream);
 

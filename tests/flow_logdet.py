@@ -8,38 +8,42 @@ import numpy as np
 from oracle import flow_oracle as fo
 
 
-def _subnet(sd, lay, block, which, u):
+def _subnet(sd, lay, block, which, u, dt=np.float64):
     base = f"module_list.{lay.glow_module(block)}.subnet{which}."
-    slope = np.float64(np.float32(fo.LEAKY_SLOPE))
+    slope = dt(np.float32(fo.LEAKY_SLOPE))
     h = u
     for layer in range(lay.n_hidden + 1):
-        h = h @ np.asarray(sd[f"{base}{2 * layer}.weight"], dtype=np.float64).T + np.asarray(sd[f"{base}{2 * layer}.bias"], dtype=np.float64)
+        h = h @ np.asarray(sd[f"{base}{2 * layer}.weight"], dtype=dt).T + np.asarray(sd[f"{base}{2 * layer}.bias"], dtype=dt)
         if layer != lay.n_hidden:
             h = np.where(h > 0, h, slope * h)
     return h
 
 
-def forward_with_logdet(sd, lay, x, cond):
-    """[n x D] rows, [n x dim_cond] conditional -> (z [n x D], log|det dz/dx| [n]), float64."""
+def forward_with_logdet(sd, lay, x, cond, dt=np.float64):
+    """[n x D] rows, [n x dim_cond] conditional -> (z [n x D], log|det dz/dx| [n]), float64.  dt=np.float32: the same arithmetic in float32
+    (log|det M| still fp64, rounded once) - the rounding noise of an f32 evaluation, for the cases where that noise itself exceeds the
+    tolerances (trained-like gains)."""
     L1, L2 = lay.dim // 2, lay.dim - lay.dim // 2
-    clamp = np.float64(np.float32(lay.clamp))
-    gain = np.float64(np.float32(fo.GLOW_ATAN_GAIN))
-    M = np.asarray(sd["module_list.0.M"], dtype=np.float64)
-    b = np.asarray(sd["module_list.0.b"], dtype=np.float64).reshape(-1)
-    c = np.asarray(cond, dtype=np.float64)
-    v = np.asarray(x, dtype=np.float64) @ M + b
-    ld = np.full(v.shape[0], np.linalg.slogdet(M)[1])
+    clamp = dt(np.float32(lay.clamp))
+    gain = dt(np.float32(fo.GLOW_ATAN_GAIN))
+    # (a state_dict without M: its inverse from M_inv, as the oracle's forward does)
+    M = (np.asarray(sd["module_list.0.M"], dtype=np.float64) if "module_list.0.M" in sd
+         else np.linalg.inv(np.asarray(sd["module_list.0.M_inv"], dtype=np.float64)))
+    b = np.asarray(sd["module_list.0.b"], dtype=dt).reshape(-1)
+    c = np.asarray(cond, dtype=dt)
+    v = np.asarray(x, dtype=dt) @ M.astype(dt) + b
+    ld = np.full(v.shape[0], np.linalg.slogdet(M)[1], dtype=dt)
     if lay.sigmoid_on_output:
-        ld = ld - np.sum(np.log(v * (1.0 - v)), 1)
-        v = np.log(v / (1.0 - v))
+        ld = ld - np.sum(np.log(v * (dt(1) - v)), 1)
+        v = np.log(v / (dt(1) - v))
     for i in range(lay.nb_nodes):
         perm = np.argsort(np.asarray(sd[f"module_list.{lay.perm_module(i)}.perm_inv"], dtype=np.int64))
         v = v[:, perm]
         x1, x2 = v[:, :L1], v[:, L1:]
-        r2 = _subnet(sd, lay, i, 2, np.concatenate([x2, c], 1))
+        r2 = _subnet(sd, lay, i, 2, np.concatenate([x2, c], 1), dt)
         s2 = clamp * gain * np.arctan(r2[:, :L1])
         y1 = np.exp(s2) * x1 + r2[:, L1:]
-        r1 = _subnet(sd, lay, i, 1, np.concatenate([y1, c], 1))
+        r1 = _subnet(sd, lay, i, 1, np.concatenate([y1, c], 1), dt)
         s1 = clamp * gain * np.arctan(r1[:, :L2])
         y2 = np.exp(s1) * x2 + r1[:, L2:]
         ld = ld + s2.sum(1) + s1.sum(1)
