@@ -76,6 +76,7 @@ __device__ __forceinline__ void ro_barrier() {
 // value of new-state element d of row `row` after the pending coupling of subnet `sm` (or the plain state when sm == null).
 // FWD (k_flow_rowowner_fwd): the coupling runs forward, y = exp(s) x + t, and the permutation of the table sits on the subnet-1 entries
 // (PermuteRandom of the NEXT block, see rowowner_fwd_table); ld (nullable) accumulates the clamped s of the elements this thread rewrites.
+// Inverse pass with a log-determinant (k_flow_rowowner_ld): ld (nullable) accumulates MINUS the clamped s - the inverse map's share.
 template <bool FWD = false>
 __device__ __forceinline__ float ro_new_state(const float* __restrict__ xs_old, const float* __restrict__ red, const float* __restrict__ sm,
                                               int row, int d, int L1, float clamp, float* ld = nullptr) {
@@ -99,6 +100,7 @@ __device__ __forceinline__ float ro_new_state(const float* __restrict__ xs_old, 
       if (ld != nullptr) *ld += s_cl;
     } else {
       v = (v - tt) * expf(-s_cl);
+      if (ld != nullptr) *ld -= s_cl;
     }
   }
   return v;
@@ -119,7 +121,10 @@ __device__ __forceinline__ unsigned ro_fwd_offset(unsigned lin, int n_sub) {
 // (k_flow_rowowner_fwd, ikflow/model.py:300-354): rows of x -> FixedLinearTransform (x.mm(M) + b; logit on sigmoid graphs) ->
 // PermuteRandom(0) -> per block: subnet 2, subnet 1, PermuteRandom of the next block -> z, plus the per-row log-determinant.  Same LDS map,
 // same stream and ring; only the schedule (ro_fwd_offset), the coupling (ro_new_state<true>), the head and the tail differ.
-template <int NBUF, bool FWD>
+// LD (with FWD = false): the inverse pass that also returns log|det dx/dz| (k_flow_rowowner_ld, ikf_flow_inverse): the inverse body
+// unchanged, the couplings' -s_cl collected as in the forward pass, and a tail that writes all D columns (RoFwd::z_out), the sliced q
+// (RoArgs::q_out, nullable here) and the row's log-determinant (RoFwd::ld_out; RoFwd::log_det0 = log|det M_inv|).
+template <int NBUF, bool FWD, bool LD = false>
 __device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
   static_assert(RO_SUB_GROUPS % NBUF == 0 && RO_KG % NBUF == 0, "ring length must divide the subnet's group count");
   constexpr int PF = NBUF - 1;
@@ -156,7 +161,7 @@ __device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
   for (int s = 0; s < PF; ++s) RO_ISSUE(s)
 
   // ---- rows: state, conditional, per-subnet small parameters -> LDS
-  float ld = 0.f;   // (FWD, threads 0..255) this thread's share of its row's log-determinant
+  float ld = 0.f;   // (FWD / LD, threads 0..255) this thread's share of its row's log-determinant
   if (t < 256) {
     const int row = t >> 4, d = t & 15;
     int gr = m0 + row;
@@ -195,7 +200,7 @@ __device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
   auto advance = [&](const float* pend_sm, const float* nxt_sm, const float* xs_old, float* xs_new) {
     if (t < 256) {
       const int row = t >> 4, d = t & 15;
-      if (d < a.D) xs_new[row * 16 + d] = ro_new_state<FWD>(xs_old, red, pend_sm, row, d, a.L1, a.clamp, FWD ? &ld : nullptr);
+      if (d < a.D) xs_new[row * 16 + d] = ro_new_state<FWD>(xs_old, red, pend_sm, row, d, a.L1, a.clamp, (FWD || LD) ? &ld : nullptr);
     } else if (nxt_sm != nullptr) {
       const int row = (t - 256) >> 4, k = t & 15;
       const int* ni = reinterpret_cast<const int*>(nxt_sm);
@@ -324,6 +329,40 @@ __device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
       s += __shfl_xor(s, 1, 16);
       if (f.ld_out != nullptr && live && d == 0) f.ld_out[m0 + row] = f.log_det0 + s;
     }
+  } else if constexpr (LD) {
+    // ---- FixedLinearTransform rev on ALL D columns: the unclamped row -> z_out, [:, :ndof] (+ clamp) -> q_out, and the log-determinant of
+    // the inverse map: log|det M_inv| + the row's 16 shares (minus the clamped s of every coupling; on sigmoid graphs + log(v (1 - v)),
+    // v = sigmoid(x), of the thread's own element, as -|x| - 2 log1p(exp(-|x|)): no cancellation for large |x|), same butterfly as FWD
+    if (t < 256) {
+      const int row = t >> 4, j = t & 15;
+      const bool live = m0 + row < a.M;
+      const float* x = xs + 256 * xcur + row * 16;
+      if (j < a.D) {
+        float q = 0.f;
+        for (int k = 0; k < a.D; ++k) {
+          float xv = x[k];
+          if (a.sigmoid) xv = 1.0f / (1.0f + expf(-xv));
+          q = fmaf(xv - a.b_lin[k], a.M_inv[k * a.D + j], q);
+        }
+        if (a.sigmoid) {
+          const float ax = fabsf(x[j]);
+          ld += -ax - 2.0f * log1pf(expf(-ax));
+        }
+        if (live) {
+          if (f.z_out != nullptr) f.z_out[(size_t)(m0 + row) * a.D + j] = q;
+          if (a.q_out != nullptr && j < a.ndof) {
+            if (a.clamp_limits) q = fminf(fmaxf(q, a.lo[j]), a.hi[j]);
+            a.q_out[(size_t)(m0 + row) * a.ndof + j] = q;
+          }
+        }
+      }
+      float s = ld;
+      s += __shfl_xor(s, 8, 16);
+      s += __shfl_xor(s, 4, 16);
+      s += __shfl_xor(s, 2, 16);
+      s += __shfl_xor(s, 1, 16);
+      if (f.ld_out != nullptr && live && j == 0) f.ld_out[m0 + row] = f.log_det0 + s;
+    }
   } else if (t < 256) {
     // ---- FixedLinearTransform rev: (x - b).mm(M_inv); [:, :ndof]; clamp_to_joint_limits
     const int row = t >> 4, j = t & 15;
@@ -356,6 +395,13 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner(RoArgs a) {
 template <int NBUF>
 __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner_fwd(RoArgs a, RoFwd f) {
   ro_flow_body<NBUF, true>(a, f);
+}
+
+// The inverse pass with its log-determinant (ikf_flow_inverse): a.sub = the inverse-order table, a.x0 = latent rows, a.q_out nullable;
+// f.z_out = the unclamped x rows [M][D], f.ld_out, f.log_det0 = log|det M_inv| (f.M / f.perm0 unused).  Any batch size, no cluster form.
+template <int NBUF>
+__global__ __launch_bounds__(RO_WAVES * 64) void k_flow_rowowner_ld(RoArgs a, RoFwd f) {
+  ro_flow_body<NBUF, false, true>(a, f);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1034,6 +1080,15 @@ hipError_t launch_flow_rowowner_fwd(const RoArgs& a, const RoFwd& f, hipStream_t
   hipError_t e = ensure_dynamic_lds(k_flow_rowowner_fwd<4>, RO_LDS_BYTES, done);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_flow_rowowner_fwd<4>, dim3(grid), dim3(RO_WAVES * 64), RO_LDS_BYTES, s, a, f);
+  return hipGetLastError();
+}
+
+hipError_t launch_flow_rowowner_ld(const RoArgs& a, const RoFwd& f, hipStream_t s) {
+  static bool done[64] = {};
+  const unsigned grid = (unsigned)((a.M + RO_ROWS - 1) / RO_ROWS);
+  hipError_t e = ensure_dynamic_lds(k_flow_rowowner_ld<4>, RO_LDS_BYTES, done);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_flow_rowowner_ld<4>, dim3(grid), dim3(RO_WAVES * 64), RO_LDS_BYTES, s, a, f);
   return hipGetLastError();
 }
 

@@ -156,6 +156,7 @@ struct ikf_model {
   float* d_M = nullptr;                // [D][D] FixedLinearTransform forward matrix (module_list.0.M, or the fp64 inverse of M_inv)
   int* d_perm = nullptr;               // [nb_nodes][D] PermuteRandom forward: perm[perm_inv[k]] = k
   float log_det_M = 0.f;               // logDetM = log|det M|, fp64 at load
+  float log_det_Minv = 0.f;            // log|det M_inv| of the M_inv that is uploaded (ikf_flow_inverse), fp64 at load - not -log_det_M
   RoSubnet* d_ro_sub_fwd = nullptr;    // the row-owner table in forward execution order (rowowner_fwd_table)
   float* d_blin = nullptr;             // [D]
   Chain* d_chain = nullptr;            // robot chain + limits
@@ -738,6 +739,26 @@ extern "C" ikf_status ikf_load_weights(ikf_model* m, const ikf_tensor* tensors, 
         for (int k = 0; k < D; ++k) M64[(size_t)r * D + k] = X[(size_t)r * D + k] / A[(size_t)r * D + r];
     }
   }
+  // the inverse pass reports the Jacobian of the map it computes: log|det M_inv| from the f32 M_inv itself (M and M_inv of a file are
+  // not exact inverses of each other), fp64 elimination with partial pivoting
+  double log_det_inv = 0.0;
+  {
+    std::vector<double> A = Minv64;
+    for (int c = 0; c < D; ++c) {
+      int p = c;
+      for (int r = c + 1; r < D; ++r)
+        if (fabs(A[(size_t)r * D + c]) > fabs(A[(size_t)p * D + c])) p = r;
+      if (A[(size_t)p * D + c] == 0.0) return fail(IKF_ERR_BAD_ARGUMENT, "ikf_load_weights: module_list.0.M_inv is singular");
+      if (p != c)
+        for (int k = 0; k < D; ++k) std::swap(A[(size_t)p * D + k], A[(size_t)c * D + k]);
+      log_det_inv += log(fabs(A[(size_t)c * D + c]));
+      for (int r = c + 1; r < D; ++r) {
+        const double f = A[(size_t)r * D + c] / A[(size_t)c * D + c];
+        if (f == 0.0) continue;
+        for (int k = c; k < D; ++k) A[(size_t)r * D + k] -= f * A[(size_t)c * D + k];
+      }
+    }
+  }
   std::vector<float> M32((size_t)D * D);
   for (int k = 0; k < D * D; ++k) M32[k] = (float)M64[k];
   std::vector<int> perm_fwd((size_t)NB * D);
@@ -759,6 +780,7 @@ extern "C" ikf_status ikf_load_weights(ikf_model* m, const ikf_tensor* tensors, 
   IKF_HIP(hipMemcpy(m->d_M, M32.data(), sizeof(float) * D * D, hipMemcpyHostToDevice));
   IKF_HIP(hipMemcpy(m->d_perm, perm_fwd.data(), sizeof(int) * (size_t)NB * D, hipMemcpyHostToDevice));
   m->log_det_M = (float)log_det;
+  m->log_det_Minv = (float)log_det_inv;
   IKF_HIP(hipMemcpy(m->d_blin, blin.data(), sizeof(float) * D, hipMemcpyHostToDevice));
   for (int si = 0; si < 2 * NB; ++si) {
     SubnetWeights& s = subs[si];
@@ -1767,6 +1789,95 @@ extern "C" ikf_status ikf_flow_forward(ikf_model* m, const float* d_x, int64_t n
     for (long long r0 = 0; st == IKF_OK && r0 < n; r0 += m->chunk_rows) {
       const long long nr = n - r0 < m->chunk_rows ? n - r0 : m->chunk_rows;
       st = run_forward_chunk_per_layer(m, ps, d_x, r0, nr, d_z_out, d_log_det_out, s);
+    }
+  }
+  if (st != IKF_OK) return st;
+  IKF_HIP(scope.leave());
+  return IKF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// inverse pass with its log-determinant: nn_model(latent, c=cond, rev=True) -> (output_rev, log_jac_det) (ikflow_solver.py:98)
+// ---------------------------------------------------------------------------------------------------------------
+// The released width (1024, 3 hidden layers): one k_flow_rowowner_ld launch for any batch size (never the cluster form).  Every other shape:
+// the per-layer kernels, chunked (state in xbuf, running log-det in xbuf2).  Always the f32 contractions, like ikf_flow_forward.
+static ikf_status run_inverse_ld_rowowner(ikf_model* m, const PoseSource& ps, const float* d_latent, long long rows, int clamp_limits,
+                                          float* d_x, float* d_q, float* d_ld, hipStream_t s) {
+  const long long kMaxLaunchRows = 1LL << 24;
+  const FlowDims& d = m->dims;
+  for (long long r0 = 0; r0 < rows; r0 += kMaxLaunchRows) {
+    const long long nr = rows - r0 < kMaxLaunchRows ? rows - r0 : kMaxLaunchRows;
+    RoArgs a = rowowner_args(m, ps, d_latent, r0, nr, clamp_limits, nullptr);
+    a.q_out = d_q ? d_q + (size_t)r0 * d.ndof : nullptr;
+    RoFwd f{};
+    f.log_det0 = m->log_det_Minv;
+    f.z_out = d_x ? d_x + (size_t)r0 * d.D : nullptr;
+    f.ld_out = d_ld ? d_ld + r0 : nullptr;
+    IKF_HIP(launch_flow_rowowner_ld(a, f, s));
+  }
+  return IKF_OK;
+}
+static ikf_status run_inverse_ld_chunk_per_layer(ikf_model* m, const PoseSource& ps, const float* d_latent, long long r0, long long nr,
+                                                 int clamp_limits, float* d_x, float* d_q, float* d_ld, hipStream_t s) {
+  const FlowDims& d = m->dims;
+  const int NB = m->desc.nb_nodes;
+  const int variant = pick_variant(m, nr);
+  for (int b = NB - 1; b >= 0; --b) {
+    for (int which = 1; which <= 2; ++which) {
+      const SubnetWeights& w = m->subnets[2 * b + which - 1];
+      const bool first = b == NB - 1 && which == 1;
+      const float* x_src = first ? d_latent + (size_t)r0 * d.D : m->xbuf;
+      IKF_HIP(launch_first_layer(w, d, x_src, which == 1 ? 0 : d.L1, ps, r0, nr, m->hA, s));
+      float* cur = m->hA;
+      float* nxt = m->hB;
+      for (int l = 0; l < d.n_hidden - 1; ++l) {
+        IKF_HIP(launch_gemm_lrelu(variant, cur, w.w_mid[l], w.b_mid[l], nxt, nr, d.width, d.width, d.slope, s));
+        float* tmp = cur; cur = nxt; nxt = tmp;
+      }
+      InvCouplingArgs ca{};
+      ca.x_in = x_src;
+      ca.state = m->xbuf;
+      ca.perm_inv = m->d_perm_inv + (size_t)b * d.D;
+      ca.ld = m->xbuf2;
+      ca.which = which;
+      ca.first = first ? 1 : 0;
+      IKF_HIP(launch_last_layer_coupling_inv(w, d, cur, ca, nr, s));
+    }
+  }
+  InvExitArgs ea{};
+  ea.state = m->xbuf; ea.ld = m->xbuf2;
+  ea.M_inv = m->d_Minv; ea.b_lin = m->d_blin; ea.lo = chain_lo(m); ea.hi = chain_hi(m);
+  ea.log_det0 = m->log_det_Minv;
+  ea.D = d.D; ea.ndof = d.ndof; ea.sigmoid = m->desc.sigmoid_on_output ? 1 : 0; ea.clamp_limits = clamp_limits;
+  ea.x_out = d_x ? d_x + (size_t)r0 * d.D : nullptr;
+  ea.q_out = d_q ? d_q + (size_t)r0 * d.ndof : nullptr;
+  ea.ld_out = d_ld ? d_ld + r0 : nullptr;
+  IKF_HIP(launch_inv_exit(ea, nr, s));
+  return IKF_OK;
+}
+
+extern "C" ikf_status ikf_flow_inverse(ikf_model* m, const float* d_latent, int64_t n, const float* d_poses, int pose_broadcast,
+                                       float softflow_scale, int clamp_to_limits, float* d_x_out, float* d_q_out,
+                                       float* d_log_det_out, void* stream) {
+  ikf_status st = check_ready(m, "ikf_flow_inverse");
+  if (st != IKF_OK) return st;
+  if (n < 0) return fail(IKF_ERR_BAD_ARGUMENT, "ikf_flow_inverse: n must be >= 0");
+  if (n == 0) return IKF_OK;
+  if (!d_latent || !d_poses) return fail(IKF_ERR_NULL_POINTER, "ikf_flow_inverse: null device pointer");
+  if (!d_x_out && !d_q_out && !d_log_det_out)
+    return fail(IKF_ERR_NULL_POINTER, "ikf_flow_inverse: d_x_out, d_q_out and d_log_det_out are all null");
+  IKF_ON_DEVICE(m)
+  PoseSource ps{d_poses, nullptr, pose_broadcast ? 1 : (long long)n, 7, softflow_scale};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  StreamScope scope(m, s);
+  IKF_HIP(scope.enter());
+  if (m->ro_stream != nullptr && m->d_ro_sub != nullptr) {   // (the row-owner image exists: the released shape)
+    st = run_inverse_ld_rowowner(m, ps, d_latent, n, clamp_to_limits, d_x_out, d_q_out, d_log_det_out, s);
+  } else {
+    st = ensure_scratch(m, n);
+    for (long long r0 = 0; st == IKF_OK && r0 < n; r0 += m->chunk_rows) {
+      const long long nr = n - r0 < m->chunk_rows ? n - r0 : m->chunk_rows;
+      st = run_inverse_ld_chunk_per_layer(m, ps, d_latent, r0, nr, clamp_to_limits, d_x_out, d_q_out, d_log_det_out, s);
     }
   }
   if (st != IKF_OK) return st;

@@ -101,6 +101,32 @@ struct FwdCouplingArgs {
 hipError_t launch_last_layer_coupling_fwd(const SubnetWeights& w, const FlowDims& d, const float* h_in, const FwdCouplingArgs& ca,
                                           long long rows, hipStream_t s);
 
+// flow_inverse.hip - the inverse pass WITH its log-determinant (ikf_flow_inverse) on the per-layer kernels (shapes without the row-owner launch)
+struct InvCouplingArgs {
+  const float* x_in;     // [rows][D] which == 1: the state this subnet reads (the caller's latent rows for the first executed block, else = state)
+  float* state;          // [rows][D] state buffer owned by the engine
+  const int* perm_inv;   // [D] PermuteRandom rev of this block (which == 2 only)
+  float* ld;             // [rows] running log-det of the inverse map
+  int which;             // 1 (runs first in a block: rewrites x2) or 2 (rewrites x1, then the permutation)
+  int first;             // first executed subnet of the pass: ld starts from its share instead of adding to it
+};
+hipError_t launch_last_layer_coupling_inv(const SubnetWeights& w, const FlowDims& d, const float* h_in, const InvCouplingArgs& ca,
+                                          long long rows, hipStream_t s);
+struct InvExitArgs {     // sigmoid (+ its log-det term), (x - b).mm(M_inv) on all D columns, the three outputs (each nullable)
+  const float* state;    // [rows][D]
+  const float* ld;       // [rows]
+  const float* M_inv;    // [D][D]
+  const float* b_lin;    // [D]
+  const float* lo;       // [ndof]
+  const float* hi;
+  float log_det0;        // log|det M_inv|
+  int D, ndof, sigmoid, clamp_limits;
+  float* x_out;          // [rows][D] unclamped
+  float* q_out;          // [rows][ndof] sliced, clamped when clamp_limits
+  float* ld_out;         // [rows]
+};
+hipError_t launch_inv_exit(const InvExitArgs& a, long long rows, hipStream_t s);
+
 // flow_fused.hip - the three-kernel-per-subnet form: the last Linear is reduced to per-tile partial sums in the epilogue
 // of the last hidden contraction, and the affine-coupling update runs at the head of the NEXT subnet's entry kernel.
 constexpr int IKF_PSTRIDE = 16;  // floats per row in one partial-sum slot
@@ -255,7 +281,7 @@ struct RoArgs {
   const unsigned* run_if;  // null, or a device word: the launch does nothing unless it is non-zero (the cluster form's repair launch)
 };
 
-struct RoFwd {             // k_flow_rowowner_fwd only: the forward pass's own inputs and outputs
+struct RoFwd {             // k_flow_rowowner_fwd: the forward pass's own inputs and outputs (k_flow_rowowner_ld: z_out = x rows, log_det0 = log|det M_inv|)
   const float* M;          // [D][D] FixedLinearTransform forward: v = x.mm(M) + b (b = RoArgs::b_lin)
   const int* perm0;        // [16] PermuteRandom(seed=0) forward: state[d] = v[perm0[d]]
   float log_det0;          // logDetM (fp64 at load, stored f32)
@@ -296,6 +322,9 @@ hipError_t launch_rowowner_pack(const SubnetWeights& w, float* out, hipStream_t 
 hipError_t launch_flow_rowowner(const RoArgs& a, int nbuf, hipStream_t s);
 // the forward (training-direction) pass in one launch (ikf_flow_forward): a.sub = the forward-order subnet table, a.x0 = joint rows
 hipError_t launch_flow_rowowner_fwd(const RoArgs& a, const RoFwd& f, hipStream_t s);
+// the inverse pass with its log-determinant in one launch (ikf_flow_inverse): a.sub = the inverse-order table, a.x0 = latent rows, a.q_out nullable;
+// f.z_out = unclamped x rows, f.ld_out, f.log_det0 = log|det M_inv|
+hipError_t launch_flow_rowowner_ld(const RoArgs& a, const RoFwd& f, hipStream_t s);
 const char* rowowner_kernel_name();
 
 // flow_split.hip - the hidden contraction on the f16 matrix cores with an error-compensated operand split:

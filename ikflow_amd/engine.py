@@ -247,6 +247,30 @@ class Engine:
             )
         return z, log_det
 
+    # -- inverse pass with its log-determinant ---------------------------------------------------------
+    def flow_inverse(self, latent: torch.Tensor, poses: torch.Tensor, softflow_scale: float = 0.0,
+                     clamp: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """latent [n x D]; poses [n x 7] or [7] (broadcast) -> (x [n x D] all columns, unclamped; q [n x ndof] = x[:, :ndof], clamped
+        to the joint limits when `clamp`; log_det [n] = log|det dx/dz|) in one pass (ikf_flow_inverse)."""
+        latent = self._on_device(latent, "latent")
+        poses = self._on_device(poses, "y")
+        n = latent.shape[0]
+        assert latent.ndim == 2 and latent.shape[1] == self.layout.dim, f"latent must be [n x {self.layout.dim}], got {tuple(latent.shape)}"
+        broadcast = poses.numel() == 7
+        if not broadcast:
+            assert poses.ndim == 2 and poses.shape[1] == 7 and poses.shape[0] == n, f"{poses.shape[0]} != {n}"
+        x = torch.empty((n, self.layout.dim), dtype=torch.float32, device=self.device)
+        q = torch.empty((n, self.layout.ndof), dtype=torch.float32, device=self.device)
+        log_det = torch.empty((n,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(
+                self.lib.ikf_flow_inverse(
+                    self._h, latent.data_ptr(), n, poses.data_ptr(), 1 if broadcast else 0, float(softflow_scale),
+                    1 if clamp else 0, x.data_ptr(), q.data_ptr(), log_det.data_ptr(), self._stream(),
+                )
+            )
+        return x, q, log_det
+
     # -- kinematics ----------------------------------------------------------------------------------
     def _q(self, q: torch.Tensor) -> torch.Tensor:
         q = self._on_device(q, "q")

@@ -290,6 +290,72 @@ class IKFlowSolver:
         z, log_det = self.engine(x.device).flow_forward(x, poses)
         return 0.5 * (z * z).sum(1) - log_det
 
+    # -- sampling with the log-likelihood (inverse pass with its log-determinant) -----------------------------
+    def nn_inverse(self, z: torch.Tensor, conditional: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The reference's ``nn_model(z, c=conditional, rev=True)`` (ikflow_solver.py:98) with BOTH of its values: z [n x dim_tot] latent
+        rows, conditional [n x dim_cond] = [pose (7), softflow scale (softflow models)] -> (x [n x dim_tot] - every column, before
+        ``[:, :ndof]`` and before any joint-limit clamp -, log|det dx/dz| [n]).  The engine takes ONE softflow scale per call: a softflow
+        column that varies across rows is refused."""
+        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
+        n = z.shape[0]
+        assert conditional.ndim == 2 and conditional.shape[0] == n and conditional.shape[1] in (7, 8), (
+            f"conditional must be [{n} x 7 or 8], got {tuple(conditional.shape)}")
+        scale = 0.0
+        if conditional.shape[1] == 8 and n > 0:
+            col = conditional[:, 7]
+            scale = float(col[0].item())
+            assert bool((col == col[0]).all().item()), "the softflow column must hold one value for every row"
+        poses = conditional[:, :7].contiguous()
+        x, _, log_det = self.engine(z.device).flow_inverse(z, poses, scale, clamp=False)
+        return x, log_det
+
+    def sample_and_log_prob(
+        self,
+        y: torch.Tensor,
+        n: Optional[int] = None,
+        latent: Optional[torch.Tensor] = None,
+        latent_distribution: str = "gaussian",
+        latent_scale: float = 1.0,
+        clamp_to_joint_limits: bool = False,
+        return_pad: bool = False,
+    ):
+        """Draw IK solutions as ``generate_ik_solutions`` does (same arguments, same ``draw_latent`` call: with the same torch seed both
+        methods see the same latent) and return, from the same single pass, the model's log-density of every sample.
+
+        Returns (solutions [n x ndof], log_prob [n]), plus pad [n x (dim_tot - ndof)] when ``return_pad``.  With x = g(z; y) the full
+        dim_tot-column output of the flow, log_prob = log p(x | y) = -0.5 |z|^2 - 0.5 dim_tot log(2 pi) - log|det dx/dz|: exactly what
+        ``log_prob(x[:, :ndof], y, pad=x[:, ndof:])`` returns for that row, without the second pass.  It is the MODEL's density at the
+        sample, not the proposal's: with ``latent_scale != 1`` or ``latent_distribution="uniform"`` the samples are not drawn from it
+        (use it as the target density of an importance weight).  It belongs to the UNCLAMPED row: with ``clamp_to_joint_limits=True`` a
+        clamped solution is a different point and ``log_prob`` still refers to the row before the clamp."""
+        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
+        assert isinstance(y, torch.Tensor), f"y must be a torch.Tensor (got {type(y)})."
+        if y.numel() == 7:
+            assert isinstance(n, int)
+            assert n > 0
+        else:
+            assert y.shape[1] == 7, f"y must be of shape [7] or [n x 7], got {y.shape}"
+        assert isinstance(latent_distribution, str)
+        assert isinstance(latent_scale, float)
+        assert isinstance(latent, torch.Tensor) or (
+            latent is None
+        ), f"latent must either be a torch.Tensor or None (got {type(latent)})."
+        if "cuda" in str(config.DEVICE):
+            assert "cpu" not in str(y.device), f"Cuda is available ('{config.DEVICE}'), but target_poses are on {y.device}"
+
+        n = y.shape[0] if n is None else n
+        device = y.device
+        with torch.inference_mode():
+            if latent is None:
+                latent = draw_latent(latent_distribution, latent_scale, (n, self._network_width), device)
+            assert latent.shape[0] == n, f"{len(latent)} != {n}"
+            x, solutions, log_det = self.engine(latent.device).flow_inverse(latent, y, 0.0, clamp=clamp_to_joint_limits)
+            dim = self._network_width
+            log_prob = -0.5 * (latent * latent).sum(1) - 0.5 * dim * float(np.log(2.0 * np.pi)) - log_det
+            if return_pad:
+                return solutions, log_prob, x[:, self._robot.ndof:].contiguous()
+            return solutions, log_prob
+
     # -- weights -------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict_filename: str):
         """Set the model's weights from a pickled state_dict (ikflow_solver.py:413-441) or a .npz with the same keys."""

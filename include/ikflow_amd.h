@@ -7,8 +7,7 @@
  * The reference has no FFI of its own (pure Python on FrEIA / jrl / torch); the entry points below are what a
  * ctypes binding inside ikflow/ikflow_solver.py would call instead of `self.nn_model(latent, c=cond, rev=True)`
  * (:98), `robot.forward_kinematics` (:114), `geodesic_distance_between_quaternions` (:116),
- * `robot.inverse_kinematics_step_levenburg_marquardt` (:205,208) and `robot.clamp_to_joint_limits` (:102).
- * INTEGRATION.md shows that binding.
+ * `robot.inverse_kinematics_step_levenburg_marquardt` (:205,208) and `robot.clamp_to_joint_limits` (:102); see INTEGRATION.md.
  *
  * Measurement / tuning entry points (kernel timing, form selection) are in ikflow_amd_debug.h - not part of this boundary.
  *
@@ -107,9 +106,8 @@ int ikf_abi_version(void);
 ikf_status ikf_load_weights(ikf_model* m, const ikf_tensor* tensors, int n_tensors);
 int ikf_weights_loaded(const ikf_model* m);
 
-/* Pre-size the flow scratch for batches of up to max_rows flow rows, and build every weight image a call of that size can reach on this
- * handle (the small-batch per-layer kernels' image included - the form a cluster-form handle falls back to while another process holds
- * CUs): after ikf_load_weights + ikf_reserve no ikf_generate_approx call of <= max_rows rows allocates or synchronises the device. */
+/* Pre-size the flow scratch for batches of up to max_rows flow rows and build every weight image a call of that size can reach on this handle (the
+ * small-batch per-layer image included): after ikf_load_weights + ikf_reserve no flow call of <= max_rows rows allocates or synchronises the device. */
 ikf_status ikf_reserve(ikf_model* m, int64_t max_rows);
 /* Pre-size the exact-IK state for max_poses target poses x max_repeat repeats, so that ikf_generate_exact allocates nothing.
  * Without it a call reserves its own worst case (n * max(repeat_counts) rows) up front while that is at most
@@ -126,6 +124,11 @@ ikf_status ikf_generate_approx(ikf_model* m, const float* d_poses, int pose_broa
 /* GraphINN forward (model.py:300-354): d_x [n x D], d_poses as above -> d_z_out [n x D], d_log_det_out [n], nullable; f32 in either precision */
 ikf_status ikf_flow_forward(ikf_model* m, const float* d_x, int64_t n, const float* d_poses, int pose_broadcast,
                             float softflow_scale, float* d_z_out, float* d_log_det_out, void* stream);
+/* GraphINN rev with its Jacobian (ikflow_solver.py:98 keeps only the first value): d_latent [n x D], d_poses as above -> d_x_out [n x D] (all columns,
+ * unclamped), d_q_out [n x ndof] (sliced; clamped when clamp_to_limits), d_log_det_out [n] = log|det dx/dz|; each nullable, not all; f32 in either precision */
+ikf_status ikf_flow_inverse(ikf_model* m, const float* d_latent, int64_t n, const float* d_poses, int pose_broadcast,
+                            float softflow_scale, int clamp_to_limits, float* d_x_out, float* d_q_out,
+                            float* d_log_det_out, void* stream);
 
 /* -- kinematics: replace the jrl.Robot calls ---------------------------------------------------------------- */
 /* robot.forward_kinematics (ikflow_solver.py:114): [n x ndof] -> [n x 7]. */
@@ -145,10 +148,9 @@ ikf_status ikf_clamp_to_joint_limits(ikf_model* m, const float* d_q, int64_t n, 
 ikf_status ikf_joint_limits_exceeded(ikf_model* m, const float* d_q, int64_t n, uint8_t* d_exceeded_out,
                                      void* stream);
 
-/* Capsule self-collision: the mechanism behind evaluation_utils.calculate_self_collisions (ikflow/evaluation_utils.py:115-126;
- * the reference delegates to jrl / Klampt geometry that is not in this repository - the caller supplies the capsules).  A
- * capsule is a segment p0-p1 with a radius in the frame that follows an actuated joint (0 = base, j + 1 = after joint j);
- * pairs = 2 * n_pairs capsule indices; a configuration collides when any listed pair is closer than r_a + r_b. */
+/* Capsule self-collision: the mechanism behind evaluation_utils.calculate_self_collisions (ikflow/evaluation_utils.py:115-126; the reference
+ * delegates to jrl / Klampt geometry that is not in this repository - the caller supplies the capsules).  A capsule is a segment p0-p1 with a radius in
+ * the frame that follows an actuated joint (0 = base, j + 1 = after joint j); pairs = 2 * n_pairs indices; colliding = a listed pair closer than r_a + r_b. */
 typedef struct ikf_capsule {
   int32_t frame;
   float p0[3];
@@ -221,17 +223,15 @@ int ikf_get_precision(const ikf_model* m);
  *       2^-24 per step, the reference's own rounding noise. */
 ikf_status ikf_set_lm_precision(ikf_model* m, int mode);
 int ikf_get_lm_precision(const ikf_model* m);
-/* Range guard of mode 1.  guard = 1 (default): every call ends by reading the flag (4-byte copy + stream synchronisation) and,
- * if set, runs again on the exact-f32 path (counted).  guard = 0: no synchronisation, no re-run; the flag accumulates on the
- * device until ikf_split_overflow_pending() reads and clears it (synchronises `stream`). */
+/* Range guard of mode 1.  guard = 1 (default): every call ends by reading the flag (4-byte copy + stream synchronisation) and, if set, runs again on the
+ * exact-f32 path (counted).  guard = 0: no synchronisation, no re-run; the flag accumulates until ikf_split_overflow_pending() reads and clears it. */
 ikf_status ikf_set_split_guard(ikf_model* m, int guard);
 /* Number of calls re-run on the f32 path because the f16 range was exceeded (guard = 1). */
 int64_t ikf_split_fallback_count(const ikf_model* m);
 /* 1 if an activation left the f16 range since the last check (then cleared), 0 if not; synchronises `stream`. */
 int ikf_split_overflow_pending(ikf_model* m, void* stream);
-/* Cluster form (workgroups of one launch exchange activations): number of calls in which a wait ran out - a peer workgroup was not
- * resident, i.e. the device is shared or partitioned.  Such a call's rows were recomputed by the row-owner launch queued behind it (the
- * caller's results are valid), and the handle stopped using the form.  Meaningful once the stream of those calls has been synchronised. */
+/* Cluster form (workgroups of one launch exchange activations): number of calls in which a wait ran out - a peer workgroup was not resident (shared or
+ * partitioned device).  Their rows were recomputed by the row-owner launch queued behind (results valid); meaningful once that stream is synchronised. */
 int64_t ikf_cluster_repairs(ikf_model* m);
 
 #ifdef __cplusplus
