@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_pose_error(const Chain* __restrict__ ch
 
 template <int NDOF, typename T>
 __global__ __launch_bounds__(256) void k_lm_step(const Chain* __restrict__ ch, const float* __restrict__ tgt,
-                                                 const float* __restrict__ q, long long n, float* __restrict__ q_out) {
+                                                 const float* q, long long n, float* q_out) {   // q_out may be q (ikflow_amd.h): no __restrict__ on the two
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   float qv[NDOF];
@@ -82,8 +82,8 @@ __global__ __launch_bounds__(256) void k_jacobian(const Chain* __restrict__ ch, 
   }
 }
 
-__global__ __launch_bounds__(256) void k_clamp(const Chain* __restrict__ ch, int ndof, const float* __restrict__ q,
-                                               long long total, float* __restrict__ q_out) {
+__global__ __launch_bounds__(256) void k_clamp(const Chain* __restrict__ ch, int ndof, const float* q,
+                                               long long total, float* q_out) {   // q_out may be q (ikflow_amd.h): no __restrict__ on the two
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int j = (int)(i % ndof);

@@ -133,9 +133,10 @@ ikf_status ikf_flow_inverse(ikf_model* m, const float* d_latent, int64_t n, cons
 /* -- kinematics: replace the jrl.Robot calls ---------------------------------------------------------------- */
 /* robot.forward_kinematics (ikflow_solver.py:114): [n x ndof] -> [n x 7]. */
 ikf_status ikf_forward_kinematics(ikf_model* m, const float* d_q, int64_t n, float* d_poses_out, void* stream);
-/* IKFlowSolver._calculate_pose_error (ikflow_solver.py:112-117): L2 position error and quaternion geodesic. */
-ikf_status ikf_pose_error(ikf_model* m, const float* d_q, const float* d_target_poses, int64_t n,
-                          float* d_pos_err, float* d_rot_err, void* stream);
+/* IKFlowSolver._calculate_pose_error (ikflow_solver.py:112-117): L2 position error and quaternion geodesic.  The rotation error (also of
+ * ikf_pose_distance) is the reference's f32 2 acos(clamp(<q_a, q_b>)) with its noise at small angles - one ulp of the dot product is worth 2.4e-7 / theta: measured
+ * against fp64 within 2e-5 above 0.15 rad, up to 9.3e-4 off below 0.01 rad (the reference's f32 result is as far); identical poses give 9.77e-4 .. 2.2e-3, not 0. */
+ikf_status ikf_pose_error(ikf_model* m, const float* d_q, const float* d_target_poses, int64_t n, float* d_pos_err, float* d_rot_err, void* stream);
 /* robot.inverse_kinematics_step_levenburg_marquardt(target_poses, q) with jrl defaults (lambda 1e-4, alpha 1,
  * clamped) (ikflow_solver.py:205,208). d_q_out may alias d_q. */
 ikf_status ikf_lm_step(ikf_model* m, const float* d_target_poses, const float* d_q, int64_t n, float* d_q_out,
@@ -145,8 +146,7 @@ ikf_status ikf_jacobian(ikf_model* m, const float* d_q, int64_t n, float* d_jac_
 /* robot.clamp_to_joint_limits (ikflow_solver.py:101-102). d_q_out may alias d_q. */
 ikf_status ikf_clamp_to_joint_limits(ikf_model* m, const float* d_q, int64_t n, float* d_q_out, void* stream);
 /* evaluation_utils.calculate_joint_limits_exceeded (evaluation_utils.py:100-112): strict inequalities. */
-ikf_status ikf_joint_limits_exceeded(ikf_model* m, const float* d_q, int64_t n, uint8_t* d_exceeded_out,
-                                     void* stream);
+ikf_status ikf_joint_limits_exceeded(ikf_model* m, const float* d_q, int64_t n, uint8_t* d_exceeded_out, void* stream);
 
 /* Capsule self-collision: the mechanism behind evaluation_utils.calculate_self_collisions (ikflow/evaluation_utils.py:115-126; the reference
  * delegates to jrl / Klampt geometry that is not in this repository - the caller supplies the capsules).  A capsule is a segment p0-p1 with a radius in

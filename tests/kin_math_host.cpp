@@ -24,6 +24,8 @@ static void run(const Chain* ch, int what, const float* tgt, const float* q, lon
 extern "C" int kin_math_host(const void* chain, int what, const float* tgt, const float* q, long long n, float* out, float* out2) {
   const Chain* ch = static_cast<const Chain*>(chain);
   switch (ch->ndof) {
+    case 4: run<4>(ch, what, tgt, q, n, out, out2); return 0;
+    case 5: run<5>(ch, what, tgt, q, n, out, out2); return 0;
     case 6: run<6>(ch, what, tgt, q, n, out, out2); return 0;
     case 7: run<7>(ch, what, tgt, q, n, out, out2); return 0;
     case 8: run<8>(ch, what, tgt, q, n, out, out2); return 0;

@@ -1,7 +1,10 @@
 """GPU parity tests: the HIP path (through the C-ABI) against the oracle on the same seeded inputs.
 
 Tolerances: flow joint angles 1e-5 absolute vs the PyTorch-CPU fp32 oracle (BASELINE.json north_star), also bounded
-by the fp64 twin; FK 2e-6; LM step vs the fp64 twin 5e-6 (the kernel solves in fp64 internally).
+by the fp64 twin; FK 2e-6; LM step vs the fp64 twin 5e-6 (the kernel solves in fp64 internally).  The 5e-6 holds for Panda, FetchArm and
+Fetch with seeds up to 0.15 rad off the truth (steps of a few tenths of a radian); it is not a property of the step: the chain constants are
+folded in f32, and that rounding grows with the step (1 rad seeds, 5- and 6-joint chains: up to 1.4e-4).  tests/test_kinematics.py holds those
+inputs to the f32 oracle's own distance from fp64 instead.
 """
 import os
 
