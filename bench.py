@@ -10,12 +10,18 @@ seeded random (nn.Linear default init) of the released architecture `panda__full
 is a remote URL and there is no network.  With N > 1 every rank processes its own 4096-row shard (weak scaling) and the
 step ends with the one RCCL all-gather of the [4096 x 7] solutions.
 
-Rank 0 prints ONE JSON line: metric/value/unit per BASELINE.json, `roofline` for the dominant kernel (k_flow_rowowner: the whole
-inverse pass of the batch in one launch, FP32-MFMA bound; `frac` from the steady-state mean launch duration of a rocprofv3 kernel
-trace of this command, `frac_event` from hipEvent pairs around the launches inside real calls), `cpu_baseline` (the torch-CPU oracle timed on this host's cores on
-a bounded sample; N=1 only), and - N=1 only, bounded to about a minute - `extra.cells`: the other cells of BASELINE.json's
-metric ("approx + exact, batch 512/4096", FetchArm B=8192), each with ms, rate, flow rows/s and its own fraction of the
-FP32-MFMA roofline.
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs - set-up, the warm-up, the K timed steps, the dump if asked
+for - and its line carries metric/value/unit per BASELINE.json, `ms_per_step`, the configuration, what first use cost, and the end-to-end
+fraction of the FP32-MFMA roofline that `value` itself implies (`roofline`, no run of its own).  A multi-rank line also carries `rccl`, the
+proof that N ranks on N devices gathered each other's rows.
+
+`--full` adds everything else the benchmark measures or checks, after the timed steps: `roofline` of the dominant kernel (k_flow_rowowner:
+the whole inverse pass of the batch in one launch, FP32-MFMA bound; `frac` from the steady-state mean launch duration of a rocprofv3 kernel
+trace of this command, `frac_event` from hipEvent pairs around the launches inside real calls, HBM traffic and occupancy from rocprofv3
+counter passes), `extra.f16x3_split` (the same workload in the other precision), `cpu_baseline` (the torch-CPU oracle timed on this host's
+cores on a bounded sample; N=1 only), - N=1 only, bounded to about a minute - `extra.cells`: the other cells of BASELINE.json's metric
+("approx + exact, batch 512/4096", FetchArm B=8192), each with ms, rate, flow rows/s and its own fraction of the FP32-MFMA roofline, and -
+N>1 only - `extra.scaling_modes`, the two strong-scaling readings.  The `--no-*` options leave single legs out of a `--full` run.
 
 `--dump-outputs DIR`: after the timed steps, rank 0 writes the solutions the last timed step returned (all ranks' rows when N > 1) to
 DIR/solutions.npy in float32; every input is seeded, so two builds run with the same arguments can be compared output for output.
@@ -51,6 +57,10 @@ def parse():
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--batch", type=int, default=4096, help="target poses per GPU per step")
     p.add_argument("--model", type=str, default=MODEL)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure and check everything beside the headline: per-launch roofline of the dominant kernel "
+                        "(hipEvent pairs, rocprofv3 trace and counter passes), the f16x3 precision, the other cells of the metric, the CPU "
+                        "baselines, the strong-scaling readings of a multi-rank run; the --no-* options below leave single legs out of it")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=16.0, help="bound on the approximate-IK CPU-baseline sample")
     p.add_argument("--gemm-variant", type=int, default=-1)
@@ -423,7 +433,7 @@ def live_profile(kernel_substr="k_flow_gemm<"):
         out["note"] = "rocprofv3 not found"
         return out
     sub = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-split-extra",
-           "--no-cells", "--no-live-pmc"]
+           "--no-cells", "--no-live-pmc", "--full"]
 
     def run(flags, steps="3", warmup="1"):
         d = tempfile.mkdtemp(prefix="ikf_prof_", dir="/tmp")
@@ -791,12 +801,71 @@ def main():
     rccl = None
     if use_dist:
         assert torch.equal(stepper.last_gathered()[rank * B : (rank + 1) * B], sol)  # own shard sits at its rank offset
+    asked = asked_global_batch(mode, world, B, args.global_batch)  # strong modes: ceil(G / world) rows per rank, the padding is not counted
+    value = asked * args.steps / elapsed
+    flow_tflops = value / world * layout.flops_per_solution() / 1e12
+    dom_kernel = eng.dominant_kernel_name(B)
+    head = {
+        "metric": f"IK solutions/sec (approx), {'Panda 12-node' if 'panda' in args.model else args.model} flow, batch {B} per GPU",
+        "value": value,
+        "unit": "IK solutions/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1000.0 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak" if mode == "weak" else "strong",
+        "vs_baseline": None,
+        "dtype": "f32" if args.precision == "f32" else "f16x3 (error-compensated f16 MFMA, f32 accumulate)",
+        "data": "synthetic (seeded random weights of the released architecture; poses = FK(uniform q); N(0,1) latents)",
+        "config": {"workload": f"{args.model} generate_ik_solutions, B={B} poses per GPU per step, clamp_to_joint_limits"
+                               + (" (1,000,000 poses per step over all ranks)" if args.million else "")
+                               + (f" (fixed global batch of {args.global_batch} poses per step split over the ranks)" if mode == "strong" else ""),
+                   "global_batch": asked, "rows_per_rank": B, "padded_rows": world * B - asked, "scaling_mode": mode,
+                   "parallelism": f"rows sharded x{world}, weights replicated, 1 all-gather/step"},
+    }
+
+    def annotate(out):
+        """What every line carries beside its figures: the multi-rank proof, what was dumped, the tests-only backend's disclaimer."""
+        if rccl is not None:
+            out["rccl"] = rccl
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "rows": dumped}
+        if TEST_BACKEND:
+            out["test_backend"] = f"{TEST_BACKEND}: all {world} ranks share cuda:0 - a test of the N>1 code path, NOT a measurement"
+            out["metric"] = "TEST RUN (ranks share one GPU): no throughput claim"
+        return out
+
+    if not args.full:
+        # the plain run ends here: nothing but the headline was measured, and `roofline` is what `value` itself implies
+        if use_dist:
+            import torch.distributed as dist
+
+            rccl = collective_proof(stepper, sol, rank, world, local_rank, dev, affinity=affinity)
+            rccl["cluster_form_repairs"] = eng.cluster_repairs
+            assert rccl["gathered_shards_ok"], "a gathered shard does not carry its rank's checksum"
+            assert rccl["world_size"] == world
+        frac = flow_tflops / FP32_MFMA_PEAK_TFLOPS
+        out = dict(head,
+                   roofline={"bound": "mfma", "achieved": flow_tflops, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": frac,
+                             "frac_source": "end to end: `value` per GPU x the algorithmic FLOP per solution (every Linear of every subnet); "
+                                            "the per-launch figures of the dominant kernel - hipEvent pairs, rocprofv3 trace and counters - "
+                                            "take runs of their own: --full",
+                             "kernel": dom_kernel},
+                   extra={"cluster_repairs": int(eng.cluster_repairs), "flow_tflops_per_gpu": round(flow_tflops, 2),
+                          "frac_of_fp32_mfma_peak_end_to_end": round(frac, 4), "first_use": first_use,
+                          "not_measured": "plain run: per-launch roofline, f16x3 precision, the other cells of the metric, CPU baselines and "
+                                          "strong-scaling readings are measured by --full"})
+        if rank == 0:
+            print(json.dumps(annotate(out)), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
 
     # dominant kernel: per-launch HIP-event timing (on the engine's stream) inside a few more, otherwise identical, steps.
     #   row-owner form (k_flow_rowowner: the whole inverse pass of the batch in ONE launch - what B = 4096 runs): algorithmic FLOP per
     #     launch = rows of the launch x SURVEY 8(d)'s 101,572,608 FLOP per solution (every Linear of every subnet);
     #   per-layer form (k_flow_gemm: one hidden Linear of all rows per launch): 2 x rows x width^2.
-    dom_kernel = eng.dominant_kernel_name(B)
     # (the cluster form is a resident-row form like the row-owner launch: one timed launch per chunk of the plan does the whole pass)
     row_owner = "rowowner" in dom_kernel or "cluster" in dom_kernel
     eng.profile_begin()  # (a throw-away pass first: the event pool's first allocations stay out of the measured pairs)
@@ -833,10 +902,6 @@ def main():
         rccl["cluster_form_repairs"] = eng.cluster_repairs
         assert rccl["gathered_shards_ok"], "a gathered shard does not carry its rank's checksum"
         assert rccl["world_size"] == world
-    asked = asked_global_batch(mode, world, B, args.global_batch)  # strong modes: ceil(G / world) rows per rank, the padding is not counted
-    value = asked * args.steps / elapsed
-    flow_tflops = value / world * layout.flops_per_solution() / 1e12
-
     headline_cfg = args.batch == 4096 and args.model == MODEL and args.precision == "f32"
     ksub = ("k_flow_rowowner" if "rowowner" in dom_kernel else "k_flow_cluster") if row_owner else "k_flow_gemm<"
     traffic, traffic_src = pmc_traffic_per_launch(ksub) if headline_cfg else (None, None)
@@ -911,24 +976,7 @@ def main():
                                "inside the kernel (the reference solves in fp32), so exact-IK joint angles match the fp32 CPU "
                                "path to that path's own fp32-solve noise, not to 1e-5")
 
-    out = {
-        "metric": f"IK solutions/sec (approx), {'Panda 12-node' if 'panda' in args.model else args.model} flow, batch {B} per GPU",
-        "value": value,
-        "unit": "IK solutions/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1000.0 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak" if mode == "weak" else "strong",
-        "vs_baseline": None,
-        "dtype": "f32" if args.precision == "f32" else "f16x3 (error-compensated f16 MFMA, f32 accumulate)",
-        "data": "synthetic (seeded random weights of the released architecture; poses = FK(uniform q); N(0,1) latents)",
-        "config": {"workload": f"{args.model} generate_ik_solutions, B={B} poses per GPU per step, clamp_to_joint_limits"
-                               + (" (1,000,000 poses per step over all ranks)" if args.million else "")
-                               + (f" (fixed global batch of {args.global_batch} poses per step split over the ranks)" if mode == "strong" else ""),
-                   "global_batch": asked, "rows_per_rank": B, "padded_rows": world * B - asked, "scaling_mode": mode,
-                   "parallelism": f"rows sharded x{world}, weights replicated, 1 all-gather/step"},
+    out = dict(head, **{
         "roofline": {"bound": "mfma", "achieved": (frac_steady * FP32_MFMA_PEAK_TFLOPS) if frac_steady else achieved, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                      # `frac`: from the profiler's own clock - the steady-state mean launch duration of the rocprofv3 kernel trace (reproducible from
                      # profiles/); `frac_event`: the hipEvent pairs around the launches inside real calls; `frac_rocprof`: the trace's raw average
@@ -966,14 +1014,8 @@ def main():
                         "multi-rank run: 1,000,000 poses per step, 125,000 per GPU at N = 8). A fixed global batch of 4096 "
                         "(`--global-batch 4096`, extra.scaling_modes.strong_global_batch_4096) leaves 512 rows per GPU at N = 8 - the "
                         "launch-latency-bound small-batch regime - and is reported beside them, not as the target."),
-    }
-    if rccl is not None:
-        out["rccl"] = rccl
-    if dumped is not None:
-        out["dumped_outputs"] = {"dir": args.dump_outputs, "rows": dumped}
-    if TEST_BACKEND:
-        out["test_backend"] = f"{TEST_BACKEND}: all {world} ranks share cuda:0 - a test of the N>1 code path, NOT a measurement"
-        out["metric"] = "TEST RUN (ranks share one GPU): no throughput claim"
+    })
+    annotate(out)
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             name = MODEL_DESCRIPTIONS[args.model]["robot_name"]

@@ -408,7 +408,7 @@ def test_bench_under_torch_distributed_run_with_rccl_world_size_one(mode):
     env.pop("IKF_BENCH_TEST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-           "--no-cells", "--no-split-extra", "--no-cpu-baseline", "--no-live-pmc"] + mode
+           "--full", "--no-cells", "--no-split-extra", "--no-cpu-baseline", "--no-live-pmc"] + mode
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=root, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

@@ -2353,7 +2353,8 @@ def test_bench_two_ranks_on_one_gpu():
         port = sk.getsockname()[1]
     env = dict(os.environ, IKF_BENCH_TEST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "1024"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "1024",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=root, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -2394,6 +2395,36 @@ def test_bench_dump_outputs_is_the_timed_path_result(tmp_path):
     lat = latents(4096, lay.dim, 1)
     ref = fo.generate_ik_solutions_torch(sd, lay, robot, poses, lat).numpy()
     assert np.abs(dumps[0] - ref).max() <= 1e-5
+
+
+def test_bench_plain_run_measures_the_headline_alone_and_full_the_rest():
+    """A plain bench.py run times its steps and prints the headline line: no CPU baseline, no other precision, no other cell, no per-launch
+    figure.  --full measures those after the same timed steps (here with its slowest legs left out) under the same headline keys."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for name, flags in (("plain", []), ("full", ["--full", "--no-cells", "--no-cpu-baseline", "--no-live-pmc"])):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2"] + flags
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        found = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(found) == 1, r.stdout
+        lines[name] = found[0]
+    for out in lines.values():
+        assert out["unit"] == "IK solutions/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["n_gpus"] == 1
+        assert out["steps"] == 5 and out["warmup"] == 2 and "batch 4096 per GPU" in out["metric"]
+        assert out["value"] > 0 and abs(out["value"] - 4096 * 5 / (out["ms_per_step"] * 5e-3)) <= 1e-6 * out["value"]
+    assert lines["plain"]["metric"] == lines["full"]["metric"]
+    plain, full = lines["plain"], lines["full"]
+    assert "cpu_baseline" not in plain and "rccl" not in plain
+    assert not {"cells", "f16x3_split", "scaling_modes", "gemm_ms"} & set(plain["extra"])
+    assert "frac_event" not in plain["roofline"] and "avg_launch_ms" not in plain["roofline"]
+    assert "rowowner" in plain["roofline"]["kernel"] and 0.0 < plain["roofline"]["frac"] < 1.0
+    assert full["extra"]["f16x3_split"]["value"] > 0 and full["extra"]["gemm_ms"] > 0
+    assert 0.0 < full["roofline"]["frac_event"] < 1.0 and full["roofline"]["kernel"] == plain["roofline"]["kernel"]
 
 
 def test_repeated_interleaved_calls_are_bit_identical():

@@ -248,6 +248,10 @@ def test_bench_and_entry_contract_host_side(monkeypatch):
     a = bench.parse()
     assert (a.gpus, a.batch, a.precision, a.million, a.no_cells, a.dist_dry_run, a.no_live_pmc) == (1, 4096, "f32", False, False, False, False)
     assert 0 < a.warmup < a.steps <= 100
+    # a plain run measures the headline alone; everything else the benchmark measures or checks is behind --full
+    assert a.full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
     # the newest committed profile round is of the row-owner launch (one launch per 4096-row step: 2.8 ms, 8 x the 203 MB weight
     # stream through the eight XCD L2s); a summary of another dominant kernel is not reported as this one's
     us, src = bench.rocprof_kernel_avg_us("k_flow_rowowner")

@@ -9,7 +9,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$R
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-split-extra --no-cells --no-live-pmc"
+COMMON="--full --no-cpu-baseline --no-split-extra --no-cells --no-live-pmc"
 SQSET="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"
 # kernel-trace statistics: the default workload (B = 4096: the row-owner launch), the same batch on the per-layer kernels, and the other cells
 # (200 steps: behind every idle gap the chip needs ~10 launches / 30 ms to come back to its clock - tools/launch_timing_check.py -
@@ -41,6 +41,6 @@ done
 cd "$REPO"
 mkdir -p profiles
 for F in "$OUT"/pmc_summary*.json "$OUT"/bench_*kernel_steady.json "$OUT"/bench_*kernel_stats.csv; do cp "$F" "profiles/${R}_$(basename "$F")"; done   # so the bench below reports THIS run's figures
-python bench.py > "$OUT/bench_default.log" 2>&1; tail -1 "$OUT/bench_default.log" > "$OUT/bench_default.json"
+python bench.py --full > "$OUT/bench_default.log" 2>&1; tail -1 "$OUT/bench_default.log" > "$OUT/bench_default.json"
 python bench.py --precision f16x3 $COMMON 2>&1 | tail -1 > "$OUT/bench_f16x3.json"
 echo "profile_round: done -> $OUT"; ls -la "$OUT"
