@@ -450,7 +450,7 @@ __device__ __forceinline__ unsigned ro_xcc_id() { return __builtin_amdgcn_s_getr
 // (TAG form: no epoch words - every member writes (launch number, XCC_ID) into a word of its own at the start of every launch, one 128-byte line
 // per row tile, and nothing in the launch reads them.  A peer on another XCD keeps its plain payload stores in ITS L2: the consumer sees the old
 // parity, re-reads, and its wait runs out (code 1) - never a wrong value.  The HOST, when it folds a give-up of such a launch, reads the words
-// (ikf_api.hip cluster_fold_give_up): members of one row tile that started that launch on different XCDs make it a placement failure - the
+// (api_flow.hip cluster_fold_give_up): members of one row tile that started that launch on different XCDs make it a placement failure - the
 // handle goes back to the spread form - instead of "a peer was not resident" (pause).  The kernel has no register to spare for this: the same
 // classification inside the failure path made the G = 4 / 8 kernels spill (+ 21 % at 512 rows), and checking the words up front, in front of
 // the first payload read, cost 2.3 % (same-box A/B, tools/lib_ab.py) - for a case the census at load has never let happen.)

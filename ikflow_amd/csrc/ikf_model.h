@@ -1,0 +1,265 @@
+// The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
+// reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
+// those units only; the kernel-launch interface is ikf_internal.h.
+#pragma once
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <chrono>
+#include <cmath>
+#include <utility>
+#include <unordered_map>
+#include <vector>
+
+#include "ikf_internal.h"
+
+using namespace ikf;  // (this header is for the API units alone)
+
+#define IKF_HIP(call)                                                                                          \
+  do {                                                                                                         \
+    hipError_t e_ = (call);                                                                                    \
+    if (e_ != hipSuccess)                                                                                      \
+      return fail(IKF_ERR_HIP, std::string(#call) + " failed: " + hipGetErrorString(e_) + " (" __FILE__ ":" + \
+                                   std::to_string(__LINE__) + ")");                                            \
+  } while (0)
+
+// Every entry point runs on the handle's device and leaves the caller's current device as it found it.
+struct DeviceGuard {
+  int prev = -1;
+  hipError_t err = hipSuccess;
+  explicit DeviceGuard(int device) {
+    err = hipGetDevice(&prev);
+    if (err == hipSuccess && prev != device) err = hipSetDevice(device);
+    else if (err == hipSuccess) prev = -1;  // nothing to restore
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+#define IKF_ON_DEVICE(m)                                                                                       \
+  DeviceGuard dev_guard_((m)->device);                                                                         \
+  if (dev_guard_.err != hipSuccess)                                                                            \
+    return fail(IKF_ERR_HIP, std::string("hipSetDevice failed: ") + hipGetErrorString(dev_guard_.err));
+
+struct ikf_model {
+  int device = 0;
+  // the per-handle scratch is shared by all calls: a call that arrives on a different stream than the previous one
+  // first waits for the event recorded behind the previous call's work
+  hipEvent_t tail_event = nullptr;
+  hipStream_t tail_stream = nullptr;
+  bool tail_valid = false;
+  ikf_model_desc desc{};
+  FlowDims dims{};
+  bool loaded = false;
+  int gemm_variant = -1;  // -1 = choose by batch size
+  int tile_cfg = -1;      // fused pipeline: -1 = choose by batch size, 0..3 forced (variant 100..103)
+  int fuse_entry = 1;     // small batches: entry kernel + first hidden contraction as one launch (0: always two launches)
+  // the next subnet's entry phase in the tail of the last hidden contraction (TailSync).  OFF by default: measured slower than the
+  // k_subnet_entry launch it replaces (r03: +3.6 % per call at 4096 rows, +7.4 % at 512) - kept as a tested,
+  // bit-identical opt-in (ikf_set_gemm_variant 121) because it is the priced answer to "hand over inside the launch"
+  int tune = IKF_TUNE_DEFAULT;  // IKF_TUNE_* switches of the small-batch kernels (ikf_set_gemm_variant 150 .. 163)
+  int fuse_tail = 0;
+  // Activation stores write-through (sc1): the lines go to memory as they are written instead of sitting dirty in the XCD L2s until the
+  // launch's end flushes them (r03, tools/variant_ab.py: 3.261 -> 3.229 ms per call at 4096 rows with the contractions' stores
+  // write-through, 1.831 -> 1.796 at 2048 and 0.721 -> 0.706 at 512 with the entry kernel's too; the entry kernel's 16-byte stores do
+  // not pay at 4096 rows).  bit 0 contractions, bit 1 entry kernel; -1 = by batch size (contractions always, entry kernel <= 2048 rows)
+  int wt_stores = -1;
+  // <= 128 rows: the whole subnet chain in one launch, hand-over inside each XCD (k_flow_chain16, flow_fused.hip).  OFF by default:
+  // bit-identical to the per-layer launches but slower (r03: 0.422 against 0.365 ms per call at 128 rows, 0.362 against 0.271 at 1 row) -
+  // a hand-over inside an XCD needs the ROWS partitioned over the XCDs, so every XCD's L2 pulls the whole 4.2 MB weight matrix of every
+  // layer (8 x the traffic of the per-layer launches, whose column tiles are spread over the XCDs), and small batches are bound by
+  // exactly that stream.  Kept as the tested, priced answer to "XCD-local synchronisation".
+  //   chain_mode: 0 off, 1 on (ikf_set_gemm_variant 170 / 171); chain_census: -1 not yet taken, 0 the dispatcher does not hand 32
+  //   workgroups to each of 8 XCDs on this device (the chain is never used), 1 verified
+  int chain_mode = 0, chain_census = -1;
+  ChainSubnet* d_chain_tab = nullptr;  // [2 nb_nodes] per-subnet arguments, rebuilt when the weights or the scratch change
+  bool chain_tab_valid = false;
+  unsigned* d_chain_ctl = nullptr;     // [IKF_CHAIN_CTL_WORDS], zero between calls (the launch's last workgroup re-zeroes it)
+  unsigned* d_arrive = nullptr;  // [kArriveWords] row-tile arrival counters of the fused tail (zeroed by every call's first entry kernel)
+  int* h_give_up = nullptr;      // pinned, device-visible: set by a workgroup whose in-launch wait ran out
+  int precision = 0;      // 0: hidden contractions on the exact-f32 MFMA; 1: error-compensated 3x f16 MFMA split
+  int lm_precision = 1;   // LM step: 1 fp64 inside (Cholesky), 0 the reference's fp32 arithmetic (LU, partial pivoting) - ikf_set_lm_precision
+  uint16_t* split_arena = nullptr;  // split-32 images of the hidden Linear weights
+  std::vector<const void*> w_mid_split;  // [subnet][layer] -> device pointer (flattened: subnet*3 + layer)
+  float* split_frag_arena = nullptr;     // fragment-major copies of the split-32 images (small-batch f16-split kernel)
+  std::vector<const void*> w_mid_split_frag;
+  // fragment-major images of the hidden Linear weights (small-batch per-layer kernels, <= 512 rows): built by the first chunk that needs
+  // them, or ahead of time by ikf_reserve - a handle whose small batches run the cluster form never pays the 201 MB / the pack launches
+  float* wfrag_arena = nullptr;
+  bool wfrag_built = false;
+  double load_ms = 0.0, frag_ms = 0.0;   // host wall time of the last ikf_load_weights (device work included) / of building these images
+  std::vector<const float*> w_mid_frag;  // [subnet][layer], same flattening; null when the width does not fit
+
+  // Row-owner form (flow_rowowner.hip): the whole inverse pass of a batch in ONE launch, a workgroup per 16 rows, weights streamed past
+  // them from `ro_stream` (the subnets' parameters in execution and consumption order, +203 MB for Panda).  Taken for the full rounds of
+  // n_cu x 16 rows of a batch and for a last partial round of at least ro_min_tail rows; the rest runs on the per-layer kernels.
+  //   ro_mode: -1 by batch size, 0 never, 1 always (ikf_set_gemm_variant 180 / 181 / 182)
+  float* ro_stream = nullptr;
+  RoSubnet* d_ro_sub = nullptr;
+  int ro_mode = -1, ro_nbuf = 4;
+  int n_cu = 256;
+  long long ro_min_tail = -1;  // -1: the last partial round goes to whatever plan_tail finds cheapest; >= 0 (probes): to the row-owner launch from that many rows on
+  // Cluster form (k_flow_cluster<G>, flow_rowowner.hip) for what is left below a round: G = 8 / 4 / 2 workgroups per 16-row tile split the
+  // hidden columns and exchange activations inside the launch (<= 512 / 1024 / 2048 rows).  Every cluster launch is followed by a
+  // predicated row-owner launch of the same rows that runs only if a wait ran out (cl_abort set): results are valid either way, and the
+  // handle stops using the form (cl_give_up).   cl_mode: -1 by batch size, 0 never, 1 whenever the grid fits (ikf_set_gemm_variant 185 / 186 / 187)
+  int cl_mode = -1;
+  long long cl_rows = 0;          // row capacity of the exchange buffers
+  float* cl_xbuf = nullptr;       // [tiles][16][1024]
+  float* cl_sync = nullptr;       // partial sums, epoch words, abort word (one memset per launch)
+  // The drain-free hand-over (r05, flow_rowowner.hip TAG): every exchanged float carries its subnet's parity in the last mantissa bit, so a
+  // producer neither drains its stores nor publishes an epoch and a consumer validates what it reads.  Taken for G = 2 .. 16 (- 3 .. 4.5 %
+  // per call, and no memset in front of the launch; with 32 members the early re-reads of whole slices cost more than the epoch words).
+  // Its buffers are its own: every float in them has parity 1 between calls (created as 0xff bytes; n_sub is even), which an epoch-word
+  // launch's zeroing memset or untagged payload would break.  cl_tag_dirty: a tagged launch gave up - the buffers are re-created in front of
+  // the next one (until then every tagged launch returns at once and its repair launch does the work: the abort word stays set).
+  //   cl_tagged: 1 (default) / 0 (ikf_set_gemm_variant 193 / 192)
+  int cl_tagged = 1;
+  float* cl_xbuf_t = nullptr;
+  float* cl_sync_t = nullptr;
+  size_t cl_sync_t_bytes = 0;
+  bool cl_tag_dirty = false;
+  int* h_cl_give_up = nullptr;    // pinned, device-visible
+  int cl_drop_next = 0;           // tests: the next cluster launch runs one workgroup short (ikf_set_gemm_variant 188): its tile's waits run out
+  long long cl_repairs = 0;       // give-ups seen so far (ikf_cluster_repairs)
+  // A wait that ran out means a peer was not resident - another process's kernel held CUs just then.  That tenant may be gone a second
+  // later, so the form is not switched off for good: it sits out cl_pause plans (ikf_generate_* calls), 16 after the first give-up and
+  // twice as many after every further one (at most 65536); kClusterCleanStreak calls of the form in a row without a give-up forget the
+  // history.  ikf_cluster_backoff reports what is left of the pause.
+  long long cl_pause = 0;         // plans the form still sits out
+  long long cl_backoff = 0;       // length of the last pause (0: no give-up on record)
+  int cl_clean = 0;               // cluster calls since the last give-up
+  bool cl_used_last = false;      // the previous plan contained a cluster launch
+  int cl_census_ok = -1;          // the placement census at load: workgroups b and b + 8 k share an XCD (1) or not (0); -1 not asked
+  int cl_far_next = 0;            // tests (ikf_set_gemm_variant 191): the next XCD-local launch's workgroup 0 publishes a wrong XCC_ID
+  unsigned cl_launch_seq = 0;     // tagged + XCD-local launches carry a 24-bit sequence number in their placement words (RcArgs::launch_seq)
+  int cl_tl_nrt = 0, cl_tl_G = 0; // row tiles / members of the most recent tagged + XCD-local launch (whose placement words a give-up makes the host read)
+  unsigned* cl_tl_words = nullptr;
+  int cl_local = 1;               // G = 4 / 8 / 16: the form with a row tile's members on one XCD (hand-over through its L2); 0 after a member met a
+                                  // peer on another XCD (placement is verified in the launch, never assumed) or by ikf_set_gemm_variant 189
+
+  // packed weights (one arena)
+  float* arena = nullptr;
+  size_t arena_floats = 0;
+  std::vector<SubnetWeights> subnets;  // [2*block + (which-1)]
+  int* d_perm_inv = nullptr;           // [nb_nodes][D]
+  float* d_Minv = nullptr;             // [D][D]
+  // forward (training-direction) pass, ikf_flow_forward
+  float* d_M = nullptr;                // [D][D] FixedLinearTransform forward matrix (module_list.0.M, or the fp64 inverse of M_inv)
+  int* d_perm = nullptr;               // [nb_nodes][D] PermuteRandom forward: perm[perm_inv[k]] = k
+  float log_det_M = 0.f;               // logDetM = log|det M|, fp64 at load
+  float log_det_Minv = 0.f;            // log|det M_inv| of the M_inv that is uploaded (ikf_flow_inverse), fp64 at load - not -log_det_M
+  RoSubnet* d_ro_sub_fwd = nullptr;    // the row-owner table in forward execution order (rowowner_fwd_table)
+  float* d_blin = nullptr;             // [D]
+  Chain* d_chain = nullptr;            // robot chain + limits
+  CollisionModel* d_collision = nullptr;  // capsules + pairs (ikf_set_collision_model), or null
+
+  // scratch
+  long long chunk_rows = 0;  // capacity of the per-chunk flow scratch
+  float* xbuf = nullptr;     // [chunk][D]
+  float* xbuf2 = nullptr;    // [chunk][D]   second state buffer (fused path ping-pongs the state)
+  float* pbuf = nullptr;     // [slots][chunk][IKF_PSTRIDE] last-Linear partial sums (fused path)
+  float* pbuf_alt = nullptr; // second set for odd subnets when a subnet has ONE hidden contraction (see ensure_scratch); else == pbuf
+  float* hA = nullptr;       // [chunk][width]
+  float* hB = nullptr;
+  // exact-IK scratch
+  long long exact_rows = 0, exact_poses = 0;
+  long long exact_upfront_rows = 32LL << 20;  // ikf_set_exact_upfront_rows
+  float* ex_q = nullptr;          // [rows][ndof]
+  uint8_t* ex_row_valid = nullptr;  // [rows]
+  unsigned* ex_pose_first = nullptr;  // [poses] earliest valid iteration over a pose's repeats in the running round (early-exit hint)
+  int* ex_pose_idx = nullptr;     // [poses]
+  int* ex_block_scratch = nullptr;  // [2 * compact_blocks(poses)] per-block counts / offsets of the ordered compaction
+  int* ex_count = nullptr;        // device
+  int* h_count = nullptr;         // pinned host
+  // f16x3 range guard
+  int* d_split_flag = nullptr;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
+  int* h_split_flag = nullptr;    // pinned host
+  int split_guard = 1;
+  long long split_fallbacks = 0;
+
+  // optional per-launch HIP-event timing of the dominant kernel (ikf_profile_begin/_end)
+  bool prof_on = false;
+  std::vector<hipEvent_t> prof_ev;  // pairs
+  size_t prof_used = 0;
+  double last_event_overhead_ms = 0.0;
+};
+
+static const int kArriveWords = 256;  // >= row tiles of any launch that hands over inside the launch (<= 256 tiles)
+static const size_t kProfMaxPairs = 8192;
+static inline hipError_t prof_mark(ikf_model* m, hipStream_t s) {
+  if (!m->prof_on || m->prof_used >= 2 * kProfMaxPairs) return hipSuccess;
+  // the pool grows by whole pairs in front of a pair's FIRST record only: a hipEventCreate between a launch and its closing record
+  // would delay that record on the host - behind a 3 ms launch the first creations were seen to add 0.3 ms to the measured pair
+  if (m->prof_used >= m->prof_ev.size() && (m->prof_used & 1) == 0) {
+    for (int i = 0; i < 64; ++i) {
+      hipEvent_t e;
+      hipError_t r = hipEventCreate(&e);
+      if (r != hipSuccess) return r;
+      m->prof_ev.push_back(e);
+    }
+  }
+  if (m->prof_used >= m->prof_ev.size()) return hipErrorInvalidValue;
+  return hipEventRecord(m->prof_ev[m->prof_used++], s);
+}
+
+static inline hipError_t stream_enter(ikf_model* m, hipStream_t s) {
+  if (m->tail_valid && s != m->tail_stream) return hipStreamWaitEvent(s, m->tail_event, 0);
+  return hipSuccess;
+}
+static inline hipError_t stream_leave(ikf_model* m, hipStream_t s) {
+  if (!m->tail_event) {
+    hipError_t e = hipEventCreateWithFlags(&m->tail_event, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+  }
+  m->tail_stream = s;
+  m->tail_valid = true;
+  return hipEventRecord(m->tail_event, s);
+}
+// Records the handle's tail event behind whatever a call has enqueued, on EVERY exit path (an error return in the middle of
+// a call leaves kernels in flight that still use the shared scratch; the next call on another stream must wait for them).
+struct StreamScope {
+  ikf_model* m;
+  hipStream_t s;
+  bool armed = false;
+  StreamScope(ikf_model* m_, hipStream_t s_) : m(m_), s(s_) {}
+  hipError_t enter() {
+    hipError_t e = stream_enter(m, s);
+    armed = (e == hipSuccess);
+    return e;
+  }
+  hipError_t leave() {  // the success path: reports the record's own status
+    armed = false;
+    return stream_leave(m, s);
+  }
+  ~StreamScope() {
+    if (armed) (void)stream_leave(m, s);
+  }
+  StreamScope(const StreamScope&) = delete;
+  StreamScope& operator=(const StreamScope&) = delete;
+};
+
+static const long long kMaxChunkRows = 16384;  // keeps the [chunk x width] activations (64 MB each at width 1024) inside the 256 MB L3
+// The kernels tile the hidden width in units of 256.  Any other coeff_fn_internal_size (ikflow/model.py:51-96 accepts any)
+// is run at the next multiple of 256 with zero weights and biases in the padding: a padded unit outputs lrelu(0) = 0 and
+// feeds 0 * 0 into every later sum, so the results are those of the unpadded network exactly.
+static const int kWidthUnit = 256;
+static const int kMaxWidth = 4096;
+
+// What crosses a unit boundary (everything else is static in its unit), defined in api_handle / api_weights / api_flow in this order;
+// none of it is part of the library's ABI.
+#pragma GCC visibility push(hidden)
+namespace ikf {
+ikf_status fail(ikf_status code, const std::string& msg);  // records the message that ikf_last_error returns
+ikf_status ensure_scratch(ikf_model* m, long long rows);
+ikf_status ensure_exact_rows(ikf_model* m, long long rows);
+ikf_status ensure_exact(ikf_model* m, long long poses, long long rows);
+ikf_status ensure_cluster_scratch(ikf_model* m, long long rows);
+ikf_status build_split_weights(ikf_model* m);
+ikf_status build_frag_weights(ikf_model* m);
+ikf_status check_ready(ikf_model* m, const char* fn);
+ikf_status run_flow_guarded(ikf_model* m, PoseSource ps, const float* d_latent, long long rows, int clamp_limits, float* d_q_out, hipStream_t s);
+}  // namespace ikf
+#pragma GCC visibility pop

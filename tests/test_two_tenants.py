@@ -1,7 +1,7 @@
 """The engine next to ANOTHER process on the same GPU (r06).  Three forms in this library let workgroups of one launch depend on one another:
 the cluster form (waits for its peers: bounded, with a repair launch), and - found this round - the one-launch subnet head of shapes with ONE
 hidden contraction per subnet, which read and wrote the partial-sum buffer in the same launch and relied on all of its workgroups starting
-together (ikf_api.hip ensure_scratch: two buffers now).  A co-tenant is what breaks such assumptions, so these tests ARE two processes;
+together (api_handle.hip ensure_scratch: two buffers now).  A co-tenant is what breaks such assumptions, so these tests ARE two processes;
 they are bounded versions of tools/two_tenant_determinism.py, tools/cluster_soak.py and tools/two_tenant_soak.py (60 s each), collected last
 (conftest.py) so that no multi-process hiccup can hide a parity test."""
 import json
