@@ -14,6 +14,7 @@ IKF_MAX_DOF = 8
 IKF_MAX_DIM = 16
 IKF_MAX_ROUNDS = 8
 IKF_MAX_CAPSULES = 24
+IKF_RANK_MAX_KEEP = 16
 
 IKF_OK = 0
 IKF_ERR_NULL_POINTER = 1
@@ -52,6 +53,19 @@ class ikf_capsule(C.Structure):
     _fields_ = [("frame", C.c_int32), ("p0", C.c_float * 3), ("p1", C.c_float * 3), ("radius", C.c_float)]
 
 
+class ikf_rank_options(C.Structure):
+    _fields_ = [
+        ("n_keep", C.c_int32),
+        ("rot_weight", C.c_float),
+        ("ref_weight", C.c_float),
+        ("max_pos_err", C.c_float),
+        ("max_rot_err", C.c_float),
+        ("reject_limits", C.c_int32),
+        ("reject_collisions", C.c_int32),
+        ("min_clearance", C.c_float),
+    ]
+
+
 class ikf_tensor(C.Structure):
     _fields_ = [
         ("name", C.c_char_p),
@@ -65,7 +79,7 @@ class ikf_tensor(C.Structure):
 LATENT_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int)
 SEED_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int)
 
-# name -> (restype, argtypes); every symbol include/ikflow_amd.h declares
+# name -> (restype, argtypes); every symbol include/ikflow_amd.h and include/ikflow_amd_debug.h declare
 SIGNATURES = {
     "ikf_create": (C.c_int, [C.POINTER(ikf_model_desc), C.c_int, C.POINTER(C.c_void_p)]),
     "ikf_destroy": (None, [C.c_void_p]),
@@ -139,6 +153,21 @@ SIGNATURES = {
     "ikf_cluster_local": (C.c_int, [C.c_void_p]),
     "ikf_plan_describe_for": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "ikf_set_gemm_variant": (C.c_int, [C.c_void_p, C.c_int]),
+    "ikf_rank_chunks": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
+}
+
+# ... every symbol include/ikflow_amd_rank.h declares (best-of-K ranking: not part of the boundary a binding of the reference needs)
+_RANK_OUTPUTS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # q_out, score_out, index_out, count_out, row_score_out
+RANK_SIGNATURES = {
+    "ikf_rank_candidates": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ikf_rank_options)] + _RANK_OUTPUTS + [C.c_void_p],
+    ),
+    "ikf_generate_ranked": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ikf_rank_options)] + _RANK_OUTPUTS + [C.c_void_p],
+    ),
+    "ikf_reserve_ranked": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
 }
 
 LIB_PATH = _build.LIB_PATH
@@ -164,7 +193,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

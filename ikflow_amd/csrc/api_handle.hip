@@ -135,6 +135,10 @@ extern "C" void ikf_destroy(ikf_model* m) {
   if (m->d_blin) (void)hipFree(m->d_blin);
   if (m->d_chain) (void)hipFree(m->d_chain);
   if (m->d_collision) (void)hipFree(m->d_collision);
+  if (m->rk_q) (void)hipFree(m->rk_q);
+  if (m->rk_part_score) (void)hipFree(m->rk_part_score);
+  if (m->rk_part_index) (void)hipFree(m->rk_part_index);
+  if (m->rk_part_count) (void)hipFree(m->rk_part_count);
   if (m->ex_count) (void)hipFree(m->ex_count);
   if (m->h_count) (void)hipHostFree(m->h_count);
   if (m->d_split_flag) (void)hipFree(m->d_split_flag);

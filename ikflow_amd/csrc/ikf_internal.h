@@ -6,6 +6,7 @@
 #include "../../include/ikflow_amd.h"
 #include "../../include/ikflow_amd_debug.h"
 #include "kin_math.h"
+#include "rank_math.h"
 
 namespace ikf {
 
@@ -380,14 +381,17 @@ hipError_t launch_split32_pack(const float* d_src, long long rows, int K, void* 
 const char* split_kernel_name();
 
 // kin_kernels.hip (struct Chain and the per-row arithmetic: kin_math.h)
-// IKF_MAX_CAPSULES (24) comes from include/ikflow_amd.h
-constexpr int IKF_MAX_CAPSULE_PAIRS = IKF_MAX_CAPSULES * (IKF_MAX_CAPSULES - 1) / 2;
-struct CollisionModel {
-  int n_caps, n_pairs;
-  int frame[IKF_MAX_CAPSULES];      // 0 = base, j + 1 = the frame that follows actuated joint j
-  float p0[IKF_MAX_CAPSULES][3], p1[IKF_MAX_CAPSULES][3], radius[IKF_MAX_CAPSULES];
-  uint8_t pair_a[IKF_MAX_CAPSULE_PAIRS], pair_b[IKF_MAX_CAPSULE_PAIRS];
-};
+// the kernels templated on the chain length: CALL sees it as the constant ND
+#define IKF_NDOF_DISPATCH(ndof, CALL) \
+  switch (ndof) {                     \
+    case 4: { constexpr int ND = 4; CALL; break; } \
+    case 5: { constexpr int ND = 5; CALL; break; } \
+    case 6: { constexpr int ND = 6; CALL; break; } \
+    case 7: { constexpr int ND = 7; CALL; break; } \
+    case 8: { constexpr int ND = 8; CALL; break; } \
+    default: return hipErrorInvalidValue;          \
+  }
+// struct CollisionModel and the capsule clearance of a row: rank_math.h
 hipError_t launch_self_collision(const Chain* d_chain, const CollisionModel* d_cm, int ndof, const float* q, long long n,
                                  float* min_dist, uint8_t* colliding, hipStream_t s);
 hipError_t launch_fk(const Chain* d_chain, int ndof, const float* q, long long n, float* poses, hipStream_t s);
@@ -419,5 +423,31 @@ hipError_t launch_all_active(long long n, int* idx_out, int* count_out, hipStrea
 long long compact_blocks(long long n);
 hipError_t launch_compact_invalid(const uint8_t* valid, long long n, int* idx_out, int* count_out, int* block_scratch,
                                   hipStream_t s);
+
+
+// rank_kernels.hip - best-of-K ranking (include/ikflow_amd_rank.h; the arithmetic: rank_math.h)
+struct RankArgs {
+  const Chain* ch;
+  const CollisionModel* cm;   // read only when opt.reject_collisions
+  const float* poses;         // [m][7]
+  const float* q;             // [k * m][ndof] tile-major candidates
+  const float* q_ref;         // [m][ndof], or null
+  ikf_rank_options opt;
+  int m, k;
+  int chunks, per_chunk;      // K-chunks (rank_chunks) and repeats per chunk
+  int tile_poses;             // rank_tile_poses(m)
+  int cap_stride;             // floats of capsule scratch per thread (odd: bank spread), 0 without collisions
+  float* row_score;           // [k * m], or null
+  // one chunk: stage 1 writes the final outputs; more: the partial lists below, merged by k_rank_merge
+  float* q_out;               // [m][n_keep][ndof]
+  float* score_out;           // [m][n_keep], or null
+  int* index_out;             // [m][n_keep], or null
+  int* count_out;             // [m], or null
+  float* part_score;          // [chunks][m][n_keep]
+  int* part_index;            // [chunks][m][n_keep]
+  int* part_count;            // [chunks][m]
+};
+size_t rank_lds_bytes(const RankArgs& a);   // dynamic LDS of a stage-1 workgroup
+hipError_t launch_rank(int ndof, const RankArgs& a, hipStream_t s);
 
 }  // namespace ikf

@@ -174,6 +174,13 @@ struct ikf_model {
   int* ex_block_scratch = nullptr;  // [2 * compact_blocks(poses)] per-block counts / offsets of the ordered compaction
   int* ex_count = nullptr;        // device
   int* h_count = nullptr;         // pinned host
+  // best-of-K ranking scratch (api_rank.hip): the flow's candidate rows and the K-chunks' partial lists
+  int n_caps = 0;                 // capsules of d_collision (sizes the ranking kernel's LDS)
+  long long rk_rows = 0, rk_lists = 0;
+  float* rk_q = nullptr;          // [rows][ndof]
+  float* rk_part_score = nullptr; // [lists][IKF_RANK_MAX_KEEP]
+  int* rk_part_index = nullptr;   // [lists][IKF_RANK_MAX_KEEP]
+  int* rk_part_count = nullptr;   // [lists]
   // f16x3 range guard
   int* d_split_flag = nullptr;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
   int* h_split_flag = nullptr;    // pinned host

@@ -146,39 +146,9 @@ __global__ __launch_bounds__(256) void k_limits_exceeded_table(LimitsTable t, in
 // Capsule self-collision (the mechanism behind evaluation_utils.calculate_self_collisions, ikflow/evaluation_utils.py:
 // 115-126, which the reference delegates to jrl/Klampt).  Capsules live in the frame that follows an actuated joint
 // (frame 0 = base, frame j+1 = after joint j; fixed URDF offsets are folded on the host); a configuration collides when
-// a listed capsule pair comes closer than the sum of its radii.  One thread per row; closest points of two segments
-// after Ericson, "Real-Time Collision Detection", 5.1.9.
+// a listed capsule pair comes closer than the sum of its radii.  One thread per row; the arithmetic is capsule_clearance
+// (rank_math.h).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float segment_segment_dist(const float* p1, const float* q1, const float* p2, const float* q2) {
-  const float d1[3] = {q1[0] - p1[0], q1[1] - p1[1], q1[2] - p1[2]};
-  const float d2[3] = {q2[0] - p2[0], q2[1] - p2[1], q2[2] - p2[2]};
-  const float r[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
-  const float a = d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2];
-  const float e = d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2];
-  const float f = d2[0] * r[0] + d2[1] * r[1] + d2[2] * r[2];
-  const float EPS = 1e-12f;
-  float sN, tN;
-  if (a <= EPS && e <= EPS) {
-    sN = 0.f; tN = 0.f;
-  } else if (a <= EPS) {
-    sN = 0.f; tN = fminf(fmaxf(f / e, 0.f), 1.f);
-  } else {
-    const float c = d1[0] * r[0] + d1[1] * r[1] + d1[2] * r[2];
-    if (e <= EPS) {
-      tN = 0.f; sN = fminf(fmaxf(-c / a, 0.f), 1.f);
-    } else {
-      const float b = d1[0] * d2[0] + d1[1] * d2[1] + d1[2] * d2[2];
-      const float denom = a * e - b * b;
-      sN = denom > EPS ? fminf(fmaxf((b * f - c * e) / denom, 0.f), 1.f) : 0.f;
-      tN = (b * sN + f) / e;
-      if (tN < 0.f) { tN = 0.f; sN = fminf(fmaxf(-c / a, 0.f), 1.f); }
-      else if (tN > 1.f) { tN = 1.f; sN = fminf(fmaxf((b - c) / a, 0.f), 1.f); }
-    }
-  }
-  const float dx = r[0] + d1[0] * sN - d2[0] * tN, dy = r[1] + d1[1] * sN - d2[1] * tN, dz = r[2] + d1[2] * sN - d2[2] * tN;
-  return sqrtf(dx * dx + dy * dy + dz * dz);
-}
-
 template <int NDOF>
 __global__ __launch_bounds__(64) void k_self_collision(const Chain* __restrict__ ch, const CollisionModel* __restrict__ cm,
                                                        const float* __restrict__ q, long long n,
@@ -189,29 +159,7 @@ __global__ __launch_bounds__(64) void k_self_collision(const Chain* __restrict__
   float* w = W[threadIdx.x];
   float qv[NDOF];
   load_q<NDOF>(q, row, qv);
-  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, p[3] = {0.f, 0.f, 0.f};
-  const int nc = cm->n_caps;
-  for (int f = 0; f <= NDOF; ++f) {
-    if (f > 0) {
-      compose<float>(R, p, ch->joints[f - 1].pre);
-      apply_joint<float>(R, p, ch->joints[f - 1].kind, ch->joints[f - 1].axis, qv[f - 1]);
-    }
-    for (int c = 0; c < nc; ++c) {
-      if (cm->frame[c] != f) continue;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const float* pl = e == 0 ? cm->p0[c] : cm->p1[c];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) w[c * 6 + e * 3 + r] = R[3 * r + 0] * pl[0] + R[3 * r + 1] * pl[1] + R[3 * r + 2] * pl[2] + p[r];
-      }
-    }
-  }
-  float best = 3.0e38f;
-  for (int k = 0; k < cm->n_pairs; ++k) {
-    const int a = cm->pair_a[k], b = cm->pair_b[k];
-    const float d = segment_segment_dist(w + a * 6, w + a * 6 + 3, w + b * 6, w + b * 6 + 3) - cm->radius[a] - cm->radius[b];
-    best = fminf(best, d);
-  }
+  const float best = capsule_clearance<NDOF>(ch, cm, qv, w);   // rank_math.h: the same function k_rank_candidates calls
   if (min_dist) min_dist[row] = best;
   if (colliding) colliding[row] = best < 0.f ? 1 : 0;
 }
@@ -402,16 +350,6 @@ __global__ __launch_bounds__(256) void k_compact_write(const uint8_t* __restrict
 // launchers
 // ---------------------------------------------------------------------------------------------------------------
 static inline unsigned blocks_for(long long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
-#define IKF_NDOF_DISPATCH(ndof, CALL) \
-  switch (ndof) {                     \
-    case 4: { constexpr int ND = 4; CALL; break; } \
-    case 5: { constexpr int ND = 5; CALL; break; } \
-    case 6: { constexpr int ND = 6; CALL; break; } \
-    case 7: { constexpr int ND = 7; CALL; break; } \
-    case 8: { constexpr int ND = 8; CALL; break; } \
-    default: return hipErrorInvalidValue;          \
-  }
 
 hipError_t launch_fk(const Chain* ch, int ndof, const float* q, long long n, float* poses, hipStream_t s) {
   if (n <= 0) return hipSuccess;

@@ -346,6 +346,72 @@ class Engine:
             self._ck(self.lib.ikf_self_collision(self._h, q.data_ptr(), q.shape[0], dist.data_ptr(), col.data_ptr(), self._stream()))
         return dist, col.to(torch.bool)
 
+    # -- best-of-K ranking (include/ikflow_amd_rank.h) -----------------------------------------------------
+    @property
+    def has_collision_model(self) -> bool:
+        return bool(getattr(self, "_has_collision_model", False))
+
+    def rank_chunks(self, n_poses: int, k: int) -> int:
+        """K-chunks a ranking call of that shape is split into on this device (1: one launch writes the results)."""
+        return int(self.lib.ikf_rank_chunks(self._h, int(n_poses), int(k)))
+
+    def reserve_ranked(self, max_poses: int, max_k: int) -> None:
+        """Pre-size what generate_ranked needs for up to max_poses x max_k candidates, so that later calls allocate nothing."""
+        self._ck(self.lib.ikf_reserve_ranked(self._h, int(max_poses), int(max_k)))
+
+    @staticmethod
+    def rank_options(n_keep: int = 1, rot_weight: float = 0.01, ref_weight: float = 0.0, max_pos_err: Optional[float] = None,
+                     max_rot_err: Optional[float] = None, reject_limits: bool = True, reject_collisions: bool = False,
+                     min_clearance: float = 0.0) -> "_lib.ikf_rank_options":
+        return _lib.ikf_rank_options(
+            int(n_keep), float(rot_weight), float(ref_weight), -1.0 if max_pos_err is None else float(max_pos_err),
+            -1.0 if max_rot_err is None else float(max_rot_err), 1 if reject_limits else 0, 1 if reject_collisions else 0, float(min_clearance),
+        )
+
+    def _rank_outputs(self, m: int, k: int, n_keep: int, row_scores: bool):
+        q_out = torch.empty((m, n_keep, self.layout.ndof), dtype=torch.float32, device=self.device)
+        score = torch.empty((m, n_keep), dtype=torch.float32, device=self.device)
+        index = torch.empty((m, n_keep), dtype=torch.int32, device=self.device)
+        count = torch.empty((m,), dtype=torch.int32, device=self.device)
+        rows = torch.empty((k * m,), dtype=torch.float32, device=self.device) if row_scores else None
+        return q_out, score, index, count, rows
+
+    def _rank_inputs(self, target_poses: torch.Tensor, k: int, rows: torch.Tensor, cols: int, q_ref: Optional[torch.Tensor], opt, what: str):
+        tp = self._on_device(target_poses, "target_poses")
+        assert tp.ndim == 2 and tp.shape[1] == 7, f"target_poses must be of shape [m x 7], got {tuple(tp.shape)}"
+        m = tp.shape[0]
+        rows = self._on_device(rows, what)
+        assert rows.ndim == 2 and rows.shape == (k * m, cols), f"{what} must be [{k * m} x {cols}] (tile-major), got {tuple(rows.shape)}"
+        if q_ref is not None:
+            q_ref = self._on_device(q_ref, "q_ref")
+            assert q_ref.shape == (m, self.layout.ndof), f"q_ref must be [{m} x {self.layout.ndof}], got {tuple(q_ref.shape)}"
+        assert 1 <= opt.n_keep <= min(k, _lib.IKF_RANK_MAX_KEEP), f"n_keep must be in 1 .. min(k, {_lib.IKF_RANK_MAX_KEEP}), got {opt.n_keep}"
+        return tp, m, rows, q_ref
+
+    def rank_candidates(self, target_poses: torch.Tensor, k: int, q: torch.Tensor, opt, q_ref: Optional[torch.Tensor] = None,
+                        row_scores: bool = False):
+        """target_poses [m x 7]; q [k * m x ndof] tile-major (row r * m + j = candidate r of pose j); opt: rank_options(...)
+        -> (q_out [m x n_keep x ndof], scores [m x n_keep], repeat_index [m x n_keep] int32, n_admissible [m] int32, row_scores [k * m] or None)."""
+        tp, m, q, q_ref = self._rank_inputs(target_poses, k, q, self.layout.ndof, q_ref, opt, "q")
+        outs = self._rank_outputs(m, k, opt.n_keep, row_scores)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_rank_candidates(
+                self._h, tp.data_ptr(), m, int(k), q.data_ptr(), None if q_ref is None else q_ref.data_ptr(), C.byref(opt),
+                *[None if t is None else t.data_ptr() for t in outs], self._stream()))
+        return outs
+
+    def generate_ranked(self, target_poses: torch.Tensor, k: int, latent: torch.Tensor, clamp: bool, opt,
+                        q_ref: Optional[torch.Tensor] = None, row_scores: bool = False):
+        """The flow on latent [k * m x D] (tile-major, pose j for row r * m + j) and the ranking of its samples, without a host round trip
+        in between; same outputs as rank_candidates."""
+        tp, m, latent, q_ref = self._rank_inputs(target_poses, k, latent, self.layout.dim, q_ref, opt, "latent")
+        outs = self._rank_outputs(m, k, opt.n_keep, row_scores)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_generate_ranked(
+                self._h, tp.data_ptr(), m, int(k), latent.data_ptr(), 1 if clamp else 0, None if q_ref is None else q_ref.data_ptr(),
+                C.byref(opt), *[None if t is None else t.data_ptr() for t in outs], self._stream()))
+        return outs
+
     # -- exact IK ------------------------------------------------------------------------------------
     def generate_exact(
         self,

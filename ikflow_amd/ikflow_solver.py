@@ -19,7 +19,7 @@ from __future__ import annotations
 import pickle
 import warnings
 from time import time
-from typing import Dict, Optional, Sequence, Tuple, Union
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -37,6 +37,22 @@ from ikflow_amd.robots import Robot
 
 def mm_to_m(x: float) -> float:
     return x / 1000.0
+
+
+class RankedSolutions(NamedTuple):
+    """What generate_ranked_ik_solutions returns (row_scores only with return_row_scores=True, else the 4-tuple RankedSolutions4)."""
+    solutions: torch.Tensor      # [m x n_keep x ndof]; unfilled slots are 0
+    scores: torch.Tensor         # [m x n_keep]; unfilled slots are +inf
+    repeat_index: torch.Tensor   # [m x n_keep] int32; unfilled slots are -1
+    n_admissible: torch.Tensor   # [m] int32
+    row_scores: torch.Tensor     # [k * m], tile-major; +inf for an inadmissible candidate
+
+
+class RankedSolutions4(NamedTuple):
+    solutions: torch.Tensor
+    scores: torch.Tensor
+    repeat_index: torch.Tensor
+    n_admissible: torch.Tensor
 
 
 def draw_latent(latent_distribution: str, latent_scale: float, shape: Tuple[int, int], device):
@@ -239,6 +255,79 @@ class IKFlowSolver:
             print(f"  {int(valids.sum().item())}/{valids.numel()} valid ({time() - t0} seconds)")
             return solutions, valids
         return out
+
+    # -- best of K samples per pose ------------------------------------------------------------------------------
+    def generate_ranked_ik_solutions(
+        self,
+        y: torch.Tensor,
+        k: int,
+        n_keep: int = 1,
+        latent: Optional[torch.Tensor] = None,
+        latent_distribution: str = "gaussian",
+        latent_scale: float = 1.0,
+        clamp_to_joint_limits: bool = True,
+        rot_weight: float = mm_to_m(1) / 0.1,
+        q_ref: Optional[torch.Tensor] = None,
+        ref_weight: float = 0.0,
+        pos_error_threshold: Optional[float] = None,
+        rot_error_threshold: Optional[float] = None,
+        reject_joint_limits: bool = True,
+        reject_self_collisions: Optional[bool] = None,
+        min_clearance: float = 0.0,
+        return_row_scores: bool = False,
+    ):
+        """Draw k flow samples for every target pose, drop the inadmissible ones and return the best n_keep of each pose - flow and ranking
+        on the GPU without a host round trip (include/ikflow_amd_rank.h).
+
+        y: [7] or [m x 7].  The latent is drawn as ``draw_latent(..., (k * m, dim))``, tile-major: row r * m + j is sample r of pose j, so the
+        same torch seed gives the candidates of ``generate_ik_solutions(y.repeat((k, 1)))``.  A candidate's score is
+        ``pos_err + rot_weight * rot_err [+ ref_weight * ||q - q_ref[j]||]`` (metres; the default rot_weight is the ratio of
+        generate_exact_ik_solutions' default thresholds, 1 mm / 0.1 rad).  Inadmissible: an error not below its threshold (when given), a
+        joint strictly outside its limits (reject_joint_limits), a clearance below min_clearance (reject_self_collisions; None = when the
+        robot carries a capsule model).  Candidates are ordered by (score, sample index).
+
+        Returns the named tuple (solutions [m x n_keep x ndof], scores [m x n_keep], repeat_index [m x n_keep] int32, n_admissible [m]
+        int32[, row_scores [k * m]]); slots beyond a pose's admissible candidates hold 0 / +inf / -1."""
+        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
+        assert isinstance(y, torch.Tensor), f"y must be a torch.Tensor (got {type(y)})."
+        assert y.numel() == 7 or (y.ndim == 2 and y.shape[1] == 7), f"y must be of shape [7] or [m x 7], got {tuple(y.shape)}"
+        assert isinstance(k, int) and k > 0, f"k must be a positive int, got {k!r}"
+        assert isinstance(n_keep, int) and 1 <= n_keep <= min(k, 16), f"n_keep must be in 1 .. min(k, 16), got {n_keep!r}"
+        assert isinstance(latent_distribution, str)
+        assert isinstance(latent_scale, float)
+        assert isinstance(latent, torch.Tensor) or latent is None, f"latent must either be a torch.Tensor or None (got {type(latent)})."
+        if reject_self_collisions is None:
+            reject_self_collisions = self._robot.has_collision_model
+        assert not reject_self_collisions or self._robot.has_collision_model, (
+            "reject_self_collisions needs a collision model (Robot.set_collision_capsules)")
+        y2 = y.reshape(1, 7) if y.numel() == 7 else y
+        m = y2.shape[0]
+        assert k * m <= 2 ** 31 - 1, f"k * m must be at most 2^31 - 1, got {k * m}"
+        assert q_ref is None or (isinstance(q_ref, torch.Tensor) and (tuple(q_ref.shape) == (m, self.ndof) or (m == 1 and tuple(q_ref.shape) == (self.ndof,)))), (
+            f"q_ref must be [{m} x {self.ndof}], got {tuple(q_ref.shape) if isinstance(q_ref, torch.Tensor) else type(q_ref)}")
+        assert pos_error_threshold is None or pos_error_threshold >= 0, "pos_error_threshold must be None (no bound) or >= 0"
+        assert rot_error_threshold is None or rot_error_threshold >= 0, "rot_error_threshold must be None (no bound) or >= 0"
+        assert latent is None or tuple(latent.shape) == (k * m, self._network_width), (
+            f"latent must be [{k * m} x {self._network_width}], got {tuple(latent.shape) if latent is not None else None}")
+        if "cuda" in str(config.DEVICE):
+            assert "cpu" not in str(y.device), f"Cuda is available ('{config.DEVICE}'), but target_poses are on {y.device}"
+
+        with torch.inference_mode():
+            eng = self.engine(y.device)
+            if reject_self_collisions and getattr(eng, "_collision_source", None) is not self._robot._collision_model:
+                # the solver's own handle, not the one Robot.config_self_collides uses
+                eng.set_collision_model(*self._robot._collision_model)
+                eng._collision_source = self._robot._collision_model
+            if latent is None:
+                latent = draw_latent(latent_distribution, latent_scale, (k * m, self._network_width), y.device)
+            opt = eng.rank_options(n_keep, rot_weight, ref_weight, pos_error_threshold, rot_error_threshold, reject_joint_limits,
+                                   reject_self_collisions, min_clearance)
+            ref = None if q_ref is None else q_ref.reshape(m, self.ndof)
+            sols, scores, index, count, rows = eng.generate_ranked(y2, k, latent, clamp_to_joint_limits, opt, q_ref=ref,
+                                                                   row_scores=return_row_scores)
+        if return_row_scores:
+            return RankedSolutions(sols, scores, index, count, rows)
+        return RankedSolutions4(sols, scores, index, count)
 
     # -- log-likelihood (forward pass) ----------------------------------------------------------------------
     def _forward_inputs(self, solutions: torch.Tensor, target_poses: torch.Tensor, pad: Optional[torch.Tensor]):

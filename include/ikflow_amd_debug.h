@@ -53,6 +53,10 @@ double ikf_frag_image_time_ms(const ikf_model* m);
 /* The same decision as pure host logic - no handle, no device: a chip of n_cu CUs, the released shape in f32, the row-owner launch and
  * the cluster form allowed (1) or not (0).  (CPU tests of the planner.) */
 ikf_status ikf_plan_describe_for(int n_cu, int64_t rows, int rowowner_allowed, int cluster_allowed, char* buf, int buf_len);
+/* K-chunks that a best-of-K call (include/ikflow_amd_rank.h) of n_poses poses x k candidates is split into on this handle's device: a pure
+ * function of (n_poses, k, CU count), DESIGN.md section 4.7.  1: one launch writes the results; more: partial lists + a merge launch.
+ * 0 for a null handle. */
+int ikf_rank_chunks(const ikf_model* m, int64_t n_poses, int k);
 /* Select the flow pipeline (a tuning / test switch; every setting computes the same function):
  *   -1 auto (3-kernel-per-subnet fused form when the shape allows), 100 the same explicitly, 101..108 the fused form with tile
  *   configuration 0..7 forced, 160 with the 16 x 32 small-batch tiles forced; 0..8 the unfused 4-kernel form with that tile variant;
