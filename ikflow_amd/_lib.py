@@ -15,6 +15,7 @@ IKF_MAX_DIM = 16
 IKF_MAX_ROUNDS = 8
 IKF_MAX_CAPSULES = 24
 IKF_RANK_MAX_KEEP = 16
+IKF_PATH_MAX_K = 256
 
 IKF_OK = 0
 IKF_ERR_NULL_POINTER = 1
@@ -63,6 +64,19 @@ class ikf_rank_options(C.Structure):
         ("reject_limits", C.c_int32),
         ("reject_collisions", C.c_int32),
         ("min_clearance", C.c_float),
+    ]
+
+
+class ikf_path_options(C.Structure):
+    _fields_ = [
+        ("rot_weight", C.c_float),
+        ("max_pos_err", C.c_float),
+        ("max_rot_err", C.c_float),
+        ("reject_limits", C.c_int32),
+        ("reject_collisions", C.c_int32),
+        ("min_clearance", C.c_float),
+        ("node_weight", C.c_float),
+        ("max_joint_step", C.c_float),
     ]
 
 
@@ -170,6 +184,20 @@ RANK_SIGNATURES = {
     "ikf_reserve_ranked": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
 }
 
+# ... every symbol include/ikflow_amd_path.h declares (path IK: the cheapest path through k candidates per waypoint)
+_PATH_OUTPUTS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # path_out, index_out, cost_out, reachable_out, node_cost_out
+PATH_SIGNATURES = {
+    "ikf_path_search": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ikf_path_options)] + _PATH_OUTPUTS + [C.c_void_p],
+    ),
+    "ikf_generate_path": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(ikf_path_options)] + _PATH_OUTPUTS + [C.c_void_p],
+    ),
+    "ikf_reserve_path": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
+}
+
 LIB_PATH = _build.LIB_PATH
 _libs = {}
 
@@ -193,7 +221,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

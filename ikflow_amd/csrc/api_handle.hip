@@ -139,6 +139,9 @@ extern "C" void ikf_destroy(ikf_model* m) {
   if (m->rk_part_score) (void)hipFree(m->rk_part_score);
   if (m->rk_part_index) (void)hipFree(m->rk_part_index);
   if (m->rk_part_count) (void)hipFree(m->rk_part_count);
+  if (m->pt_node) (void)hipFree(m->pt_node);
+  if (m->pt_bp) (void)hipFree(m->pt_bp);
+  if (m->pt_latent) (void)hipFree(m->pt_latent);
   if (m->ex_count) (void)hipFree(m->ex_count);
   if (m->h_count) (void)hipHostFree(m->h_count);
   if (m->d_split_flag) (void)hipFree(m->d_split_flag);

@@ -9,7 +9,7 @@ static long long rank_list_bound(const ikf_model* m, long long poses) {
   const long long by_chunks = IKF_RANK_MAX_CHUNKS * poses, by_cus = 128LL * m->n_cu + poses;
   return by_chunks < by_cus ? by_chunks : by_cus;
 }
-static ikf_status ensure_rank_lists(ikf_model* m, long long poses) {
+ikf_status ikf::ensure_rank_lists(ikf_model* m, long long poses) {   // (also the node stage of path IK, api_path.hip)
   const long long lists = rank_list_bound(m, poses);
   if (lists <= m->rk_lists) return IKF_OK;
   if (m->rk_part_score) (void)hipFree(m->rk_part_score);
@@ -23,7 +23,7 @@ static ikf_status ensure_rank_lists(ikf_model* m, long long poses) {
   m->rk_lists = lists;
   return IKF_OK;
 }
-static ikf_status ensure_rank_rows(ikf_model* m, long long rows) {
+ikf_status ikf::ensure_rank_rows(ikf_model* m, long long rows) {   // (also the candidate rows of path IK, api_path.hip)
   if (rows <= m->rk_rows) return IKF_OK;
   if (m->rk_q) (void)hipFree(m->rk_q);
   m->rk_q = nullptr;

@@ -7,6 +7,7 @@
 #include "../../include/ikflow_amd_debug.h"
 #include "kin_math.h"
 #include "rank_math.h"
+#include "path_math.h"
 
 namespace ikf {
 
@@ -449,5 +450,21 @@ struct RankArgs {
 };
 size_t rank_lds_bytes(const RankArgs& a);   // dynamic LDS of a stage-1 workgroup
 hipError_t launch_rank(int ndof, const RankArgs& a, hipStream_t s);
+
+// path_kernels.hip - path IK (include/ikflow_amd_path.h; the arithmetic: path_math.h)
+struct PathArgs {
+  const float* q;             // [k * T][ndof] tile-major candidates
+  const float* q_start;       // [ndof], or null
+  ikf_path_options opt;
+  int T, k;
+  const float* node;          // [k * T] node costs (the ranking's row scores of the rows against their waypoints)
+  uint8_t* bp;                // [T][k] back-pointers (path_bp_bytes(T, k) bytes)
+  float* path_out;            // [T][ndof]
+  int* index_out;             // [T]
+  float* cost_out;            // [1]
+  int* reachable_out;         // [T], or null
+};
+hipError_t launch_path_expand_latent(const float* latent, int k, long long T, int D, float* out, hipStream_t s);
+hipError_t launch_path_lattice(int ndof, const PathArgs& a, hipStream_t s);
 
 }  // namespace ikf

@@ -1,6 +1,6 @@
 // The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
 // reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
-// those units only; the kernel-launch interface is ikf_internal.h.
+// those units (and api_rank / api_path) only; the kernel-launch interface is ikf_internal.h.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -181,6 +181,11 @@ struct ikf_model {
   float* rk_part_score = nullptr; // [lists][IKF_RANK_MAX_KEEP]
   int* rk_part_index = nullptr;   // [lists][IKF_RANK_MAX_KEEP]
   int* rk_part_count = nullptr;   // [lists]
+  // path IK scratch (api_path.hip; the candidate rows are rk_q): node costs and back-pointers of the lattice, the shared latent expanded
+  long long pt_rows = 0, pt_latent_rows = 0;
+  float* pt_node = nullptr;       // [rows]
+  uint8_t* pt_bp = nullptr;       // [rows] a byte per node (+ padding: path_bp_bytes)
+  float* pt_latent = nullptr;     // [latent rows][D]
   // f16x3 range guard
   int* d_split_flag = nullptr;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
   int* h_split_flag = nullptr;    // pinned host
@@ -255,7 +260,7 @@ static const long long kMaxChunkRows = 16384;  // keeps the [chunk x width] acti
 static const int kWidthUnit = 256;
 static const int kMaxWidth = 4096;
 
-// What crosses a unit boundary (everything else is static in its unit), defined in api_handle / api_weights / api_flow in this order;
+// What crosses a unit boundary (everything else is static in its unit), defined in api_handle / api_weights / api_flow / api_rank in this order;
 // none of it is part of the library's ABI.
 #pragma GCC visibility push(hidden)
 namespace ikf {
@@ -268,5 +273,7 @@ ikf_status build_split_weights(ikf_model* m);
 ikf_status build_frag_weights(ikf_model* m);
 ikf_status check_ready(ikf_model* m, const char* fn);
 ikf_status run_flow_guarded(ikf_model* m, PoseSource ps, const float* d_latent, long long rows, int clamp_limits, float* d_q_out, hipStream_t s);
+ikf_status ensure_rank_rows(ikf_model* m, long long rows);
+ikf_status ensure_rank_lists(ikf_model* m, long long poses);
 }  // namespace ikf
 #pragma GCC visibility pop

@@ -412,6 +412,65 @@ class Engine:
                 C.byref(opt), *[None if t is None else t.data_ptr() for t in outs], self._stream()))
         return outs
 
+    # -- path IK (include/ikflow_amd_path.h) --------------------------------------------------------------
+    def reserve_path(self, max_waypoints: int, max_k: int) -> None:
+        """Pre-size what generate_path needs for up to max_waypoints x max_k candidates, so that later calls allocate nothing."""
+        self._ck(self.lib.ikf_reserve_path(self._h, int(max_waypoints), int(max_k)))
+
+    @staticmethod
+    def path_options(rot_weight: float = 0.01, max_pos_err: Optional[float] = None, max_rot_err: Optional[float] = None,
+                     reject_limits: bool = True, reject_collisions: bool = False, min_clearance: float = 0.0, node_weight: float = 1.0,
+                     max_joint_step: Optional[float] = None) -> "_lib.ikf_path_options":
+        return _lib.ikf_path_options(
+            float(rot_weight), -1.0 if max_pos_err is None else float(max_pos_err), -1.0 if max_rot_err is None else float(max_rot_err),
+            1 if reject_limits else 0, 1 if reject_collisions else 0, float(min_clearance), float(node_weight),
+            -1.0 if max_joint_step is None else float(max_joint_step),
+        )
+
+    def _path_inputs(self, waypoints: torch.Tensor, k: int, rows: torch.Tensor, shared: bool, cols: int, q_start: Optional[torch.Tensor], what: str):
+        wp = self._on_device(waypoints, "waypoints")
+        assert wp.ndim == 2 and wp.shape[1] == 7, f"waypoints must be of shape [T x 7], got {tuple(wp.shape)}"
+        assert 1 <= k <= _lib.IKF_PATH_MAX_K, f"k must be in 1 .. {_lib.IKF_PATH_MAX_K}, got {k}"
+        T = wp.shape[0]
+        rows = self._on_device(rows, what)
+        n_rows = k if shared else k * T
+        assert rows.ndim == 2 and rows.shape == (n_rows, cols), f"{what} must be [{n_rows} x {cols}], got {tuple(rows.shape)}"
+        if q_start is not None:
+            q_start = self._on_device(q_start, "q_start")
+            assert q_start.shape == (self.layout.ndof,), f"q_start must be [{self.layout.ndof}], got {tuple(q_start.shape)}"
+        return wp, T, rows, q_start
+
+    def _path_outputs(self, T: int, k: int, node_costs: bool):
+        path = torch.empty((T, self.layout.ndof), dtype=torch.float32, device=self.device)
+        index = torch.empty((T,), dtype=torch.int32, device=self.device)
+        cost = torch.full((1,), float("inf"), dtype=torch.float32, device=self.device)   # (T = 0: the call writes nothing)
+        reach = torch.empty((T,), dtype=torch.int32, device=self.device)
+        nodes = torch.empty((k * T,), dtype=torch.float32, device=self.device) if node_costs else None
+        return path, index, cost, reach, nodes
+
+    def path_search(self, waypoints: torch.Tensor, k: int, q: torch.Tensor, opt, q_start: Optional[torch.Tensor] = None, node_costs: bool = False):
+        """waypoints [T x 7]; q [k * T x ndof] tile-major (row r * T + t = candidate r of waypoint t); opt: path_options(...)
+        -> (path [T x ndof], index [T] int32, cost [1], n_reachable [T] int32, node_costs [k * T] or None)."""
+        wp, T, q, q_start = self._path_inputs(waypoints, k, q, False, self.layout.ndof, q_start, "q")
+        outs = self._path_outputs(T, k, node_costs)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_path_search(
+                self._h, wp.data_ptr(), T, int(k), q.data_ptr(), None if q_start is None else q_start.data_ptr(), C.byref(opt),
+                *[None if t is None else t.data_ptr() for t in outs], self._stream()))
+        return outs
+
+    def generate_path(self, waypoints: torch.Tensor, k: int, latent: torch.Tensor, shared_latent: bool, clamp: bool, opt,
+                      q_start: Optional[torch.Tensor] = None, node_costs: bool = False):
+        """The flow on k candidates per waypoint - latent [k x D] held fixed along the path (shared_latent), or [k * T x D] tile-major - and
+        the search through them, without a host round trip in between; same outputs as path_search."""
+        wp, T, latent, q_start = self._path_inputs(waypoints, k, latent, bool(shared_latent), self.layout.dim, q_start, "latent")
+        outs = self._path_outputs(T, k, node_costs)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_generate_path(
+                self._h, wp.data_ptr(), T, int(k), latent.data_ptr(), 1 if shared_latent else 0, 1 if clamp else 0,
+                None if q_start is None else q_start.data_ptr(), C.byref(opt), *[None if t is None else t.data_ptr() for t in outs], self._stream()))
+        return outs
+
     # -- exact IK ------------------------------------------------------------------------------------
     def generate_exact(
         self,

@@ -55,6 +55,22 @@ class RankedSolutions4(NamedTuple):
     n_admissible: torch.Tensor
 
 
+class PathSolution(NamedTuple):
+    """What generate_ik_path returns (node_costs only with return_node_costs=True, else the 4-tuple PathSolution4)."""
+    path: torch.Tensor           # [T x ndof]; all 0 when there is no path
+    index: torch.Tensor          # [T] int32, the candidate chosen per waypoint; -1 when there is no path
+    cost: torch.Tensor           # [] the total of the lattice; +inf when there is no path
+    n_reachable: torch.Tensor    # [T] int32, candidates of a waypoint that some admissible path reaches
+    node_costs: torch.Tensor     # [k * T], tile-major; +inf for an inadmissible candidate
+
+
+class PathSolution4(NamedTuple):
+    path: torch.Tensor
+    index: torch.Tensor
+    cost: torch.Tensor
+    n_reachable: torch.Tensor
+
+
 def draw_latent(latent_distribution: str, latent_scale: float, shape: Tuple[int, int], device):
     """Draw a sample from the latent noise distribution (ikflow_solver.py:16-29; torch's global generator)."""
     assert latent_distribution in ["gaussian", "uniform"]
@@ -328,6 +344,91 @@ class IKFlowSolver:
         if return_row_scores:
             return RankedSolutions(sols, scores, index, count, rows)
         return RankedSolutions4(sols, scores, index, count)
+
+    # -- one joint-space path through a sequence of poses ------------------------------------------------------------
+    def generate_ik_path(
+        self,
+        waypoints: torch.Tensor,
+        k: int,
+        latent: Optional[torch.Tensor] = None,
+        shared_latent: bool = True,
+        latent_distribution: str = "gaussian",
+        latent_scale: float = 1.0,
+        clamp_to_joint_limits: bool = True,
+        rot_weight: float = mm_to_m(1) / 0.1,
+        node_weight: float = 1.0,
+        max_joint_step: Optional[float] = None,
+        q_start: Optional[torch.Tensor] = None,
+        pos_error_threshold: Optional[float] = None,
+        rot_error_threshold: Optional[float] = None,
+        reject_joint_limits: bool = True,
+        reject_self_collisions: Optional[bool] = None,
+        min_clearance: float = 0.0,
+        refine_steps: int = 0,
+        return_node_costs: bool = False,
+    ):
+        """Draw k flow samples for every waypoint of a pose sequence and return the one joint-space path through them that is cheapest in
+        pose error and joint motion - flow and search on the GPU without a host round trip (include/ikflow_amd_path.h).
+
+        waypoints: [T x 7], in order.  With shared_latent (the default) the latent is drawn as ``draw_latent(..., (k, dim))`` and candidate r
+        uses latent r at EVERY waypoint (the reference's visualizations.py oscillate_target(fixed_latent=True): under trained weights a fixed
+        latent gives a solution that varies smoothly with the pose); otherwise as ``(k * T, dim)``, tile-major (row r * T + t is candidate r
+        of waypoint t).  A candidate's node cost is ``pos_err + rot_weight * rot_err`` (metres), +inf when it is inadmissible (thresholds,
+        joint limits, self-collision as in generate_ranked_ik_solutions); the edge between consecutive candidates is their Euclidean joint
+        distance (no angle wrapping), forbidden when a joint moves by more than max_joint_step.  The path minimises
+        ``sum of edges + node_weight * sum of node costs`` (+ the edge from q_start to the first configuration when q_start is given); ties
+        go to the lower candidate index.
+
+        refine_steps > 0 applies that many Levenberg-Marquardt steps to the T chosen rows when a path exists; ``index`` and ``cost`` (and
+        ``n_reachable``, ``node_costs``) still describe the unrefined lattice.
+
+        Returns the named tuple (path [T x ndof], index [T] int32, cost, n_reachable [T] int32[, node_costs [k * T]]); without an admissible
+        path: rows 0, indices -1, cost +inf, and n_reachable shows the first waypoint nothing reaches."""
+        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
+        assert isinstance(waypoints, torch.Tensor), f"waypoints must be a torch.Tensor (got {type(waypoints)})."
+        assert waypoints.ndim == 2 and waypoints.shape[1] == 7, f"waypoints must be of shape [T x 7], got {tuple(waypoints.shape)}"
+        assert isinstance(k, int) and 1 <= k <= 256, f"k must be an int in 1 .. 256, got {k!r}"
+        assert isinstance(latent_distribution, str)
+        assert isinstance(latent_scale, float)
+        assert isinstance(latent, torch.Tensor) or latent is None, f"latent must either be a torch.Tensor or None (got {type(latent)})."
+        assert isinstance(refine_steps, int) and refine_steps >= 0, f"refine_steps must be an int >= 0, got {refine_steps!r}"
+        if reject_self_collisions is None:
+            reject_self_collisions = self._robot.has_collision_model
+        assert not reject_self_collisions or self._robot.has_collision_model, (
+            "reject_self_collisions needs a collision model (Robot.set_collision_capsules)")
+        T = waypoints.shape[0]
+        assert k * T <= 2 ** 31 - 1, f"k * T must be at most 2^31 - 1, got {k * T}"
+        assert q_start is None or (isinstance(q_start, torch.Tensor) and tuple(q_start.shape) == (self.ndof,)), (
+            f"q_start must be [{self.ndof}], got {tuple(q_start.shape) if isinstance(q_start, torch.Tensor) else type(q_start)}")
+        assert pos_error_threshold is None or pos_error_threshold >= 0, "pos_error_threshold must be None (no bound) or >= 0"
+        assert rot_error_threshold is None or rot_error_threshold >= 0, "rot_error_threshold must be None (no bound) or >= 0"
+        assert node_weight >= 0, f"node_weight must be >= 0, got {node_weight!r}"
+        assert max_joint_step is None or max_joint_step >= 0, "max_joint_step must be None (no gate) or >= 0"
+        n_latent = k if shared_latent else k * T
+        assert latent is None or tuple(latent.shape) == (n_latent, self._network_width), (
+            f"latent must be [{n_latent} x {self._network_width}], got {tuple(latent.shape) if latent is not None else None}")
+        if "cuda" in str(config.DEVICE):
+            assert "cpu" not in str(waypoints.device), f"Cuda is available ('{config.DEVICE}'), but target_poses are on {waypoints.device}"
+
+        with torch.inference_mode():
+            eng = self.engine(waypoints.device)
+            if reject_self_collisions and getattr(eng, "_collision_source", None) is not self._robot._collision_model:
+                # the solver's own handle, not the one Robot.config_self_collides uses
+                eng.set_collision_model(*self._robot._collision_model)
+                eng._collision_source = self._robot._collision_model
+            if latent is None:
+                latent = draw_latent(latent_distribution, latent_scale, (n_latent, self._network_width), waypoints.device)
+            opt = eng.path_options(rot_weight, pos_error_threshold, rot_error_threshold, reject_joint_limits, reject_self_collisions,
+                                   min_clearance, node_weight, max_joint_step)
+            path, index, cost, reach, nodes = eng.generate_path(waypoints, k, latent, shared_latent, clamp_to_joint_limits, opt,
+                                                                q_start=q_start, node_costs=return_node_costs)
+            cost = cost.reshape(())
+            if refine_steps > 0 and T > 0 and bool(torch.isfinite(cost).item()):
+                for _ in range(refine_steps):
+                    path = eng.lm_step(waypoints, path)
+        if return_node_costs:
+            return PathSolution(path, index, cost, reach, nodes)
+        return PathSolution4(path, index, cost, reach)
 
     # -- log-likelihood (forward pass) ----------------------------------------------------------------------
     def _forward_inputs(self, solutions: torch.Tensor, target_poses: torch.Tensor, pad: Optional[torch.Tensor]):
