@@ -16,6 +16,8 @@ IKF_MAX_ROUNDS = 8
 IKF_MAX_CAPSULES = 24
 IKF_RANK_MAX_KEEP = 16
 IKF_PATH_MAX_K = 256
+IKF_DIVERSE_MAX_K = 1024
+IKF_DIVERSE_MAX_KEEP = 16
 
 IKF_OK = 0
 IKF_ERR_NULL_POINTER = 1
@@ -77,6 +79,19 @@ class ikf_path_options(C.Structure):
         ("min_clearance", C.c_float),
         ("node_weight", C.c_float),
         ("max_joint_step", C.c_float),
+    ]
+
+
+class ikf_diverse_options(C.Structure):
+    _fields_ = [
+        ("n_keep", C.c_int32),
+        ("rot_weight", C.c_float),
+        ("max_pos_err", C.c_float),
+        ("max_rot_err", C.c_float),
+        ("reject_limits", C.c_int32),
+        ("reject_collisions", C.c_int32),
+        ("min_clearance", C.c_float),
+        ("min_separation", C.c_float),
     ]
 
 
@@ -198,6 +213,21 @@ PATH_SIGNATURES = {
     "ikf_reserve_path": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
 }
 
+# ... every symbol include/ikflow_amd_diverse.h declares (diverse-of-K IK: a far-apart set of each pose's admissible candidates)
+# q_out, score_out, index_out, separation_out, kept_out, count_out, row_score_out
+_DIVERSE_OUTPUTS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+DIVERSE_SIGNATURES = {
+    "ikf_diverse_select": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ikf_diverse_options)] + _DIVERSE_OUTPUTS + [C.c_void_p],
+    ),
+    "ikf_generate_diverse": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ikf_diverse_options)] + _DIVERSE_OUTPUTS + [C.c_void_p],
+    ),
+    "ikf_reserve_diverse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
+}
+
 LIB_PATH = _build.LIB_PATH
 _libs = {}
 
@@ -221,7 +251,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

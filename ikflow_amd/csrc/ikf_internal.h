@@ -8,6 +8,7 @@
 #include "kin_math.h"
 #include "rank_math.h"
 #include "path_math.h"
+#include "diverse_math.h"
 
 namespace ikf {
 
@@ -466,5 +467,22 @@ struct PathArgs {
 };
 hipError_t launch_path_expand_latent(const float* latent, int k, long long T, int D, float* out, hipStream_t s);
 hipError_t launch_path_lattice(int ndof, const PathArgs& a, hipStream_t s);
+
+// diverse_kernels.hip - diverse-of-K IK (include/ikflow_amd_diverse.h; the arithmetic: diverse_math.h)
+struct DiverseArgs {
+  const float* q;             // [k * n][ndof] tile-major candidates
+  const float* score;         // [k * n] row scores (the ranking's, +inf: inadmissible)
+  const float* w;             // [ndof] joint weights, or null
+  int n, k;                   // poses, candidates per pose
+  int n_keep;
+  float min_separation;
+  float* q_out;               // [n][n_keep][ndof]
+  float* score_out;           // [n][n_keep], or null
+  int* index_out;             // [n][n_keep]
+  float* sep_out;             // [n][n_keep], or null
+  int* kept_out;              // [n], or null
+  int* count_out;             // [n], or null
+};
+hipError_t launch_diverse_select(int ndof, const DiverseArgs& a, hipStream_t s);
 
 }  // namespace ikf

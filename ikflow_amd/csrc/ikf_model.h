@@ -1,6 +1,6 @@
 // The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
 // reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
-// those units (and api_rank / api_path) only; the kernel-launch interface is ikf_internal.h.
+// those units (and api_rank / api_path / api_diverse) only; the kernel-launch interface is ikf_internal.h.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -186,6 +186,9 @@ struct ikf_model {
   float* pt_node = nullptr;       // [rows]
   uint8_t* pt_bp = nullptr;       // [rows] a byte per node (+ padding: path_bp_bytes)
   float* pt_latent = nullptr;     // [latent rows][D]
+  // diverse-of-K scratch (api_diverse.hip; the candidate rows are rk_q, the partial lists the ranking's): the row scores
+  long long dv_rows = 0;
+  float* dv_score = nullptr;      // [rows]
   // f16x3 range guard
   int* d_split_flag = nullptr;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
   int* h_split_flag = nullptr;    // pinned host

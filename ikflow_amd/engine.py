@@ -471,6 +471,68 @@ class Engine:
                 None if q_start is None else q_start.data_ptr(), C.byref(opt), *[None if t is None else t.data_ptr() for t in outs], self._stream()))
         return outs
 
+    # -- diverse-of-K IK (include/ikflow_amd_diverse.h) ---------------------------------------------------
+    def reserve_diverse(self, max_poses: int, max_k: int) -> None:
+        """Pre-size what generate_diverse needs for up to max_poses x max_k candidates, so that later calls allocate nothing."""
+        self._ck(self.lib.ikf_reserve_diverse(self._h, int(max_poses), int(max_k)))
+
+    @staticmethod
+    def diverse_options(n_keep: int = 1, rot_weight: float = 0.01, max_pos_err: Optional[float] = None, max_rot_err: Optional[float] = None,
+                        reject_limits: bool = True, reject_collisions: bool = False, min_clearance: float = 0.0,
+                        min_separation: float = 0.0) -> "_lib.ikf_diverse_options":
+        return _lib.ikf_diverse_options(
+            int(n_keep), float(rot_weight), -1.0 if max_pos_err is None else float(max_pos_err), -1.0 if max_rot_err is None else float(max_rot_err),
+            1 if reject_limits else 0, 1 if reject_collisions else 0, float(min_clearance), float(min_separation),
+        )
+
+    def _diverse_inputs(self, target_poses: torch.Tensor, k: int, rows: torch.Tensor, cols: int, joint_weights: Optional[torch.Tensor], opt, what: str):
+        tp = self._on_device(target_poses, "target_poses")
+        assert tp.ndim == 2 and tp.shape[1] == 7, f"target_poses must be of shape [m x 7], got {tuple(tp.shape)}"
+        assert 1 <= k <= _lib.IKF_DIVERSE_MAX_K, f"k must be in 1 .. {_lib.IKF_DIVERSE_MAX_K}, got {k}"
+        m = tp.shape[0]
+        rows = self._on_device(rows, what)
+        assert rows.ndim == 2 and rows.shape == (k * m, cols), f"{what} must be [{k * m} x {cols}] (tile-major), got {tuple(rows.shape)}"
+        if joint_weights is not None:
+            joint_weights = self._on_device(joint_weights, "joint_weights")
+            assert joint_weights.shape == (self.layout.ndof,), f"joint_weights must be [{self.layout.ndof}], got {tuple(joint_weights.shape)}"
+        assert 1 <= opt.n_keep <= min(k, _lib.IKF_DIVERSE_MAX_KEEP), f"n_keep must be in 1 .. min(k, {_lib.IKF_DIVERSE_MAX_KEEP}), got {opt.n_keep}"
+        return tp, m, rows, joint_weights
+
+    def _diverse_outputs(self, m: int, k: int, n_keep: int, row_scores: bool):
+        q_out = torch.empty((m, n_keep, self.layout.ndof), dtype=torch.float32, device=self.device)
+        score = torch.empty((m, n_keep), dtype=torch.float32, device=self.device)
+        index = torch.empty((m, n_keep), dtype=torch.int32, device=self.device)
+        sep = torch.empty((m, n_keep), dtype=torch.float32, device=self.device)
+        kept = torch.empty((m,), dtype=torch.int32, device=self.device)
+        count = torch.empty((m,), dtype=torch.int32, device=self.device)
+        rows = torch.empty((k * m,), dtype=torch.float32, device=self.device) if row_scores else None
+        return q_out, score, index, sep, kept, count, rows
+
+    def diverse_select(self, target_poses: torch.Tensor, k: int, q: torch.Tensor, opt, joint_weights: Optional[torch.Tensor] = None,
+                       row_scores: bool = False):
+        """target_poses [m x 7]; q [k * m x ndof] tile-major (row r * m + j = candidate r of pose j); opt: diverse_options(...); joint_weights
+        [ndof], every one finite and >= 0 (the caller's contract) -> (q_out [m x n_keep x ndof], scores [m x n_keep], repeat_index [m x n_keep] int32,
+        separation [m x n_keep], n_kept [m] int32, n_admissible [m] int32, row_scores [k * m] or None)."""
+        tp, m, q, w = self._diverse_inputs(target_poses, k, q, self.layout.ndof, joint_weights, opt, "q")
+        outs = self._diverse_outputs(m, k, opt.n_keep, row_scores)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_diverse_select(
+                self._h, tp.data_ptr(), m, int(k), q.data_ptr(), None if w is None else w.data_ptr(), C.byref(opt),
+                *[None if t is None else t.data_ptr() for t in outs], self._stream()))
+        return outs
+
+    def generate_diverse(self, target_poses: torch.Tensor, k: int, latent: torch.Tensor, clamp: bool, opt,
+                         joint_weights: Optional[torch.Tensor] = None, row_scores: bool = False):
+        """The flow on latent [k * m x D] (tile-major, pose j for row r * m + j) and the farthest-point selection among its samples, without a
+        host round trip in between; same outputs as diverse_select."""
+        tp, m, latent, w = self._diverse_inputs(target_poses, k, latent, self.layout.dim, joint_weights, opt, "latent")
+        outs = self._diverse_outputs(m, k, opt.n_keep, row_scores)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_generate_diverse(
+                self._h, tp.data_ptr(), m, int(k), latent.data_ptr(), 1 if clamp else 0, None if w is None else w.data_ptr(),
+                C.byref(opt), *[None if t is None else t.data_ptr() for t in outs], self._stream()))
+        return outs
+
     # -- exact IK ------------------------------------------------------------------------------------
     def generate_exact(
         self,

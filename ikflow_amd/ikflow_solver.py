@@ -71,6 +71,26 @@ class PathSolution4(NamedTuple):
     n_reachable: torch.Tensor
 
 
+class DiverseSolutions(NamedTuple):
+    """What generate_diverse_ik_solutions returns (row_scores only with return_row_scores=True, else the 6-tuple DiverseSolutions6)."""
+    solutions: torch.Tensor      # [m x n_keep x ndof]; unfilled slots are 0
+    scores: torch.Tensor         # [m x n_keep]; unfilled slots are +inf
+    repeat_index: torch.Tensor   # [m x n_keep] int32; unfilled slots are -1
+    separation: torch.Tensor     # [m x n_keep] distance to the nearest row kept before it; +inf in slot 0 and in unfilled slots
+    n_kept: torch.Tensor         # [m] int32, slots filled
+    n_admissible: torch.Tensor   # [m] int32
+    row_scores: torch.Tensor     # [k * m], tile-major; +inf for an inadmissible candidate
+
+
+class DiverseSolutions6(NamedTuple):
+    solutions: torch.Tensor
+    scores: torch.Tensor
+    repeat_index: torch.Tensor
+    separation: torch.Tensor
+    n_kept: torch.Tensor
+    n_admissible: torch.Tensor
+
+
 def draw_latent(latent_distribution: str, latent_scale: float, shape: Tuple[int, int], device):
     """Draw a sample from the latent noise distribution (ikflow_solver.py:16-29; torch's global generator)."""
     assert latent_distribution in ["gaussian", "uniform"]
@@ -344,6 +364,83 @@ class IKFlowSolver:
         if return_row_scores:
             return RankedSolutions(sols, scores, index, count, rows)
         return RankedSolutions4(sols, scores, index, count)
+
+    # -- the distinct ways of reaching a pose -----------------------------------------------------------------------
+    def generate_diverse_ik_solutions(
+        self,
+        y: torch.Tensor,
+        k: int,
+        n_keep: int,
+        min_separation: float = 0.0,
+        joint_weights: Optional[torch.Tensor] = None,
+        latent: Optional[torch.Tensor] = None,
+        latent_distribution: str = "gaussian",
+        latent_scale: float = 1.0,
+        clamp_to_joint_limits: bool = True,
+        rot_weight: float = mm_to_m(1) / 0.1,
+        pos_error_threshold: Optional[float] = None,
+        rot_error_threshold: Optional[float] = None,
+        reject_joint_limits: bool = True,
+        reject_self_collisions: Optional[bool] = None,
+        min_clearance: float = 0.0,
+        return_row_scores: bool = False,
+    ):
+        """Draw k flow samples for every target pose, drop the inadmissible ones and return up to n_keep of each pose that are far apart in
+        joint space - the distinct ways of reaching the pose, as seeds for a collision checker or alternatives for a planner - flow and
+        selection on the GPU without a host round trip (include/ikflow_amd_diverse.h).
+
+        y: [7] or [m x 7]; 1 <= k <= 1024, 1 <= n_keep <= min(k, 16).  Latent layout, scores and admissibility are those of
+        generate_ranked_ik_solutions (without a reference configuration).  Slot 0 is that method's first choice; every later slot is the
+        admissible sample farthest (Euclidean in joint space, no angle wrapping; joint j scaled by a finite joint_weights[j] >= 0 when given) from
+        the ones kept so far, ties to the lower sample index.  A pose's selection stops when no sample is left or the farthest one is
+        closer than min_separation to a kept one: kept rows are pairwise at least min_separation apart, and when fewer than n_keep are
+        kept every other admissible sample is closer than that to one of them.
+
+        Returns the named tuple (solutions [m x n_keep x ndof], scores, repeat_index int32, separation [all m x n_keep], n_kept [m] int32,
+        n_admissible [m] int32[, row_scores [k * m]]); unfilled slots hold 0 / +inf / -1 / +inf."""
+        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
+        assert isinstance(y, torch.Tensor), f"y must be a torch.Tensor (got {type(y)})."
+        assert y.numel() == 7 or (y.ndim == 2 and y.shape[1] == 7), f"y must be of shape [7] or [m x 7], got {tuple(y.shape)}"
+        assert isinstance(k, int) and 1 <= k <= 1024, f"k must be an int in 1 .. 1024, got {k!r}"
+        assert isinstance(n_keep, int) and 1 <= n_keep <= min(k, 16), f"n_keep must be in 1 .. min(k, 16), got {n_keep!r}"
+        assert isinstance(min_separation, (int, float)) and min_separation >= 0, f"min_separation must be >= 0, got {min_separation!r}"
+        assert isinstance(latent_distribution, str)
+        assert isinstance(latent_scale, float)
+        assert isinstance(latent, torch.Tensor) or latent is None, f"latent must either be a torch.Tensor or None (got {type(latent)})."
+        if reject_self_collisions is None:
+            reject_self_collisions = self._robot.has_collision_model
+        assert not reject_self_collisions or self._robot.has_collision_model, (
+            "reject_self_collisions needs a collision model (Robot.set_collision_capsules)")
+        y2 = y.reshape(1, 7) if y.numel() == 7 else y
+        m = y2.shape[0]
+        assert k * m <= 2 ** 31 - 1, f"k * m must be at most 2^31 - 1, got {k * m}"
+        assert joint_weights is None or (isinstance(joint_weights, torch.Tensor) and tuple(joint_weights.shape) == (self.ndof,)), (
+            f"joint_weights must be [{self.ndof}], got {tuple(joint_weights.shape) if isinstance(joint_weights, torch.Tensor) else type(joint_weights)}")
+        assert joint_weights is None or bool((torch.isfinite(joint_weights) & (joint_weights >= 0)).all().item()), (
+            "joint_weights must all be finite and >= 0")
+        assert pos_error_threshold is None or pos_error_threshold >= 0, "pos_error_threshold must be None (no bound) or >= 0"
+        assert rot_error_threshold is None or rot_error_threshold >= 0, "rot_error_threshold must be None (no bound) or >= 0"
+        assert latent is None or tuple(latent.shape) == (k * m, self._network_width), (
+            f"latent must be [{k * m} x {self._network_width}], got {tuple(latent.shape) if latent is not None else None}")
+        if "cuda" in str(config.DEVICE):
+            assert "cpu" not in str(y.device), f"Cuda is available ('{config.DEVICE}'), but target_poses are on {y.device}"
+
+        with torch.inference_mode():
+            eng = self.engine(y.device)
+            if reject_self_collisions and getattr(eng, "_collision_source", None) is not self._robot._collision_model:
+                # the solver's own handle, not the one Robot.config_self_collides uses
+                eng.set_collision_model(*self._robot._collision_model)
+                eng._collision_source = self._robot._collision_model
+            if latent is None:
+                latent = draw_latent(latent_distribution, latent_scale, (k * m, self._network_width), y.device)
+            opt = eng.diverse_options(n_keep, rot_weight, pos_error_threshold, rot_error_threshold, reject_joint_limits,
+                                      reject_self_collisions, min_clearance, min_separation)
+            w = None if joint_weights is None else joint_weights.to(device=y.device, dtype=torch.float32)
+            sols, scores, index, sep, kept, count, rows = eng.generate_diverse(y2, k, latent, clamp_to_joint_limits, opt, joint_weights=w,
+                                                                               row_scores=return_row_scores)
+        if return_row_scores:
+            return DiverseSolutions(sols, scores, index, sep, kept, count, rows)
+        return DiverseSolutions6(sols, scores, index, sep, kept, count)
 
     # -- one joint-space path through a sequence of poses ------------------------------------------------------------
     def generate_ik_path(
