@@ -18,6 +18,8 @@ IKF_RANK_MAX_KEEP = 16
 IKF_PATH_MAX_K = 256
 IKF_DIVERSE_MAX_K = 1024
 IKF_DIVERSE_MAX_KEEP = 16
+IKF_WORLD_MAX_OBSTACLES = 64
+IKF_OBSTACLE_SPHERE, IKF_OBSTACLE_CAPSULE, IKF_OBSTACLE_HALF_SPACE, IKF_OBSTACLE_BOX = 0, 1, 2, 3
 
 IKF_OK = 0
 IKF_ERR_NULL_POINTER = 1
@@ -93,6 +95,10 @@ class ikf_diverse_options(C.Structure):
         ("min_clearance", C.c_float),
         ("min_separation", C.c_float),
     ]
+
+
+class ikf_obstacle(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("a", C.c_float * 3), ("b", C.c_float * 3), ("quat", C.c_float * 4), ("radius", C.c_float)]
 
 
 class ikf_tensor(C.Structure):
@@ -228,6 +234,14 @@ DIVERSE_SIGNATURES = {
     "ikf_reserve_diverse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
 }
 
+# ... every symbol include/ikflow_amd_world.h declares (world collision: the caller's obstacles against the robot's capsules)
+WORLD_SIGNATURES = {
+    "ikf_set_world": (C.c_int, [C.c_void_p, C.POINTER(ikf_obstacle), C.c_int, C.c_float]),
+    "ikf_world_size": (C.c_int, [C.c_void_p]),
+    # q, n, clearance_out, obstacle_out, capsule_out, colliding_out, stream
+    "ikf_world_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 LIB_PATH = _build.LIB_PATH
 _libs = {}
 
@@ -251,7 +265,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

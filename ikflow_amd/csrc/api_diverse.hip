@@ -56,6 +56,7 @@ static ikf_status run_diverse(ikf_model* m, const float* d_poses, int64_t n, int
   ra.per_chunk = (k + ra.chunks - 1) / ra.chunks;
   ra.tile_poses = rank_tile_poses(n);
   ra.cap_stride = opt->reject_collisions ? ((m->n_caps * 6) | 1) : 0;
+  rank_args_world(m, &ra);
   ra.row_score = score;
   ra.q_out = d_q_out;
   if (ra.chunks > 1) {

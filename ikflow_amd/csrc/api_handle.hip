@@ -143,6 +143,7 @@ extern "C" void ikf_destroy(ikf_model* m) {
   if (m->pt_bp) (void)hipFree(m->pt_bp);
   if (m->pt_latent) (void)hipFree(m->pt_latent);
   if (m->dv_score) (void)hipFree(m->dv_score);
+  if (m->d_world) (void)hipFree(m->d_world);
   if (m->ex_count) (void)hipFree(m->ex_count);
   if (m->h_count) (void)hipHostFree(m->h_count);
   if (m->d_split_flag) (void)hipFree(m->d_split_flag);

@@ -65,6 +65,7 @@ static ikf_status run_path(ikf_model* m, const float* d_waypoints, int64_t T, in
   ra.per_chunk = (k + ra.chunks - 1) / ra.chunks;
   ra.tile_poses = rank_tile_poses(T);
   ra.cap_stride = opt->reject_collisions ? ((m->n_caps * 6) | 1) : 0;
+  rank_args_world(m, &ra);
   ra.row_score = node;
   ra.q_out = d_path_out;
   if (ra.chunks > 1) {

@@ -33,6 +33,15 @@ ikf_status ikf::ensure_rank_rows(ikf_model* m, long long rows) {   // (also the 
   return IKF_OK;
 }
 
+// With obstacles set on the handle (ikf_set_world) every launch of k_rank_candidates - the ranking's, the node stage of path IK, the score stage
+// of diverse-of-K - takes its WORLD form; that form needs every thread's capsule slice whether or not self-collisions are rejected.
+void ikf::rank_args_world(const ikf_model* m, RankArgs* a) {
+  if (m->world_n < 1) return;
+  a->world = m->d_world;
+  a->world_min_clearance = m->world_min_clearance;
+  a->cap_stride = (m->n_caps * 6) | 1;
+}
+
 // what both entries check once the handle is known to be there; *nothing_to_do: n_poses == 0
 static ikf_status rank_check(ikf_model* m, const std::string& who, int64_t n, int k, const ikf_rank_options* opt, const void* d_poses,
                              const void* d_rows, const void* d_q_out, bool* nothing_to_do) {
@@ -65,6 +74,7 @@ static ikf_status run_rank(ikf_model* m, const float* d_poses, int64_t n, int k,
   a.per_chunk = (k + a.chunks - 1) / a.chunks;
   a.tile_poses = rank_tile_poses(n);
   a.cap_stride = opt->reject_collisions ? ((m->n_caps * 6) | 1) : 0;
+  rank_args_world(m, &a);
   a.row_score = d_row_score_out;
   a.q_out = d_q_out;
   a.score_out = d_score_out;

@@ -9,6 +9,7 @@
 #include "rank_math.h"
 #include "path_math.h"
 #include "diverse_math.h"
+#include "world_math.h"
 
 namespace ikf {
 
@@ -438,7 +439,9 @@ struct RankArgs {
   int m, k;
   int chunks, per_chunk;      // K-chunks (rank_chunks) and repeats per chunk
   int tile_poses;             // rank_tile_poses(m)
-  int cap_stride;             // floats of capsule scratch per thread (odd: bank spread), 0 without collisions
+  int cap_stride;             // floats of capsule scratch per thread (odd: bank spread), 0 without collisions and without a world
+  const WorldModel* world;    // the handle's obstacles (world_math.h), or null: no world rule
+  float world_min_clearance;  // read only with a world
   float* row_score;           // [k * m], or null
   // one chunk: stage 1 writes the final outputs; more: the partial lists below, merged by k_rank_merge
   float* q_out;               // [m][n_keep][ndof]
@@ -484,5 +487,10 @@ struct DiverseArgs {
   int* count_out;             // [n], or null
 };
 hipError_t launch_diverse_select(int ndof, const DiverseArgs& a, hipStream_t s);
+
+// world_kernels.hip - world collision (include/ikflow_amd_world.h; the arithmetic: world_math.h).  d_world null or empty: 3.0e38 / -1 / 0.
+hipError_t launch_world_clearance(const Chain* d_chain, const CollisionModel* d_cm, int n_caps, const WorldModel* d_world, int n_obs,
+                                  float min_clearance, int ndof, const float* q, long long n, float* clearance, int* obstacle, int* capsule,
+                                  uint8_t* colliding, hipStream_t s);
 
 }  // namespace ikf

@@ -1,6 +1,6 @@
 // The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
 // reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
-// those units (and api_rank / api_path / api_diverse) only; the kernel-launch interface is ikf_internal.h.
+// those units (and api_rank / api_path / api_diverse / api_world) only; the kernel-launch interface is ikf_internal.h.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -189,6 +189,10 @@ struct ikf_model {
   // diverse-of-K scratch (api_diverse.hip; the candidate rows are rk_q, the partial lists the ranking's): the row scores
   long long dv_rows = 0;
   float* dv_score = nullptr;      // [rows]
+  // world collision (api_world.hip): the caller's obstacles; with world_n > 0 the ranking kernel also rejects rows closer than world_min_clearance
+  WorldModel* d_world = nullptr;  // allocated by the first ikf_set_world with obstacles
+  int world_n = 0;
+  float world_min_clearance = 0.f;
   // f16x3 range guard
   int* d_split_flag = nullptr;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
   int* h_split_flag = nullptr;    // pinned host
@@ -278,5 +282,6 @@ ikf_status check_ready(ikf_model* m, const char* fn);
 ikf_status run_flow_guarded(ikf_model* m, PoseSource ps, const float* d_latent, long long rows, int clamp_limits, float* d_q_out, hipStream_t s);
 ikf_status ensure_rank_rows(ikf_model* m, long long rows);
 ikf_status ensure_rank_lists(ikf_model* m, long long poses);
+void rank_args_world(const ikf_model* m, RankArgs* a);   // the handle's world into a->world / world_min_clearance (and the capsule slices it needs)
 }  // namespace ikf
 #pragma GCC visibility pop

@@ -11,6 +11,9 @@
 // (a thread per pose), merges the chunks.  No atomics, no waiting between workgroups: the selection order is total, so every split gives
 // the same lists.  LDS per workgroup (dynamic): tile_poses x (2 NKEEP + 1) words for the wave hand-over (<= 8448 B) + 128 x ((6 n_caps) | 1)
 // floats of capsule end points when collisions are rejected (<= 74240 B at 24 capsules): at most 82688 B of a CU's 160 KiB.
+// WORLD (a world is set on the handle, include/ikflow_amd_world.h): the obstacle table (4096 B) is staged between the two areas, every
+// thread has its capsule slice whatever reject_collisions says, and the score is rank_row_score_world: at most 86784 B.  WORLD = false is the
+// kernel as it was.
 #include "ikf_internal.h"
 
 namespace ikf {
@@ -32,7 +35,7 @@ __device__ __forceinline__ void rank_write_final(const RankArgs& a, long long j,
   if (a.count_out) a.count_out[j] = count;
 }
 
-template <int NDOF, int NKEEP>
+template <int NDOF, int NKEEP, bool WORLD>
 __global__ __launch_bounds__(IKF_RANK_BLOCK) void k_rank_candidates(const RankArgs a) {
   extern __shared__ float rank_lds[];
   const int tp = a.tile_poses, slices = IKF_RANK_BLOCK / tp;
@@ -42,7 +45,15 @@ __global__ __launch_bounds__(IKF_RANK_BLOCK) void k_rank_candidates(const RankAr
   const int r_begin = blockIdx.y * a.per_chunk;
   const int r_end = r_begin + a.per_chunk < a.k ? r_begin + a.per_chunk : a.k;
   float* const hand = rank_lds;                                           // [2 NKEEP + 1][tp]
-  float* const w = rank_lds + tp * (2 * NKEEP + 1) + t * a.cap_stride;    // this thread's capsule end points
+  float* const w = rank_lds + tp * (2 * NKEEP + 1) + (WORLD ? IKF_WORLD_TABLE_WORDS : 0) + t * a.cap_stride;   // this thread's capsule end points
+  const WorldObstacle* const obs = reinterpret_cast<const WorldObstacle*>(rank_lds + tp * (2 * NKEEP + 1));     // WORLD: the staged table
+  int n_obs = 0;
+  if constexpr (WORLD) {
+    n_obs = a.world->n;
+    const float* const src = reinterpret_cast<const float*>(a.world->obs);
+    for (int i = t; i < n_obs * IKF_WORLD_OBSTACLE_WORDS; i += IKF_RANK_BLOCK) rank_lds[tp * (2 * NKEEP + 1) + i] = src[i];
+    __syncthreads();
+  }
 
   TopList<NKEEP> top;
   top.clear();
@@ -57,7 +68,9 @@ __global__ __launch_bounds__(IKF_RANK_BLOCK) void k_rank_candidates(const RankAr
       const long long row = (long long)r * a.m + j;
       float qv[NDOF];
       load_q<NDOF>(a.q, row, qv);
-      const float score = rank_row_score<NDOF>(a.ch, a.cm, qv, tg, qr, a.q_ref != nullptr, a.opt, w);
+      float score;
+      if constexpr (WORLD) score = rank_row_score_world<NDOF>(a.ch, a.cm, qv, tg, qr, a.q_ref != nullptr, a.opt, w, obs, n_obs, a.world_min_clearance);
+      else score = rank_row_score<NDOF>(a.ch, a.cm, qv, tg, qr, a.q_ref != nullptr, a.opt, w);
       if (a.row_score) a.row_score[row] = score;
       if (score < rank_inf()) ++count;
       top.insert(score, r);
@@ -135,20 +148,23 @@ __global__ __launch_bounds__(256) void k_rank_merge(const RankArgs a) {
 static inline int rank_keep_capacity(int n_keep) { return n_keep <= 1 ? 1 : n_keep <= 4 ? 4 : IKF_RANK_MAX_KEEP; }
 
 size_t rank_lds_bytes(const RankArgs& a) {
-  return sizeof(float) * ((size_t)a.tile_poses * (2 * rank_keep_capacity(a.opt.n_keep) + 1) + (size_t)IKF_RANK_BLOCK * a.cap_stride);
+  return sizeof(float) * ((size_t)a.tile_poses * (2 * rank_keep_capacity(a.opt.n_keep) + 1) + (a.world ? IKF_WORLD_TABLE_WORDS : 0) +
+                          (size_t)IKF_RANK_BLOCK * a.cap_stride);
 }
-constexpr size_t kRankMaxLds = sizeof(float) * (64 * (2 * IKF_RANK_MAX_KEEP + 1) + (size_t)IKF_RANK_BLOCK * (IKF_MAX_CAPSULES * 6 + 1));
+constexpr size_t kRankMaxLds =
+    sizeof(float) * (64 * (2 * IKF_RANK_MAX_KEEP + 1) + IKF_WORLD_TABLE_WORDS + (size_t)IKF_RANK_BLOCK * (IKF_MAX_CAPSULES * 6 + 1));
+static_assert(kRankMaxLds == 82688 + 4096, "hand-over area + obstacle table + capsule slices");
 static_assert(kRankMaxLds <= 160 * 1024, "a stage-1 workgroup must fit the LDS of a CU");
 
-template <int NDOF, int NKEEP>
+template <int NDOF, int NKEEP, bool WORLD>
 static hipError_t launch_rank_as(const RankArgs& a, hipStream_t s) {
   static bool lds_opt_in[64];
   const size_t lds = rank_lds_bytes(a);
   if (lds > 48 * 1024) {
-    if (hipError_t e = ensure_dynamic_lds(k_rank_candidates<NDOF, NKEEP>, kRankMaxLds, lds_opt_in); e != hipSuccess) return e;
+    if (hipError_t e = ensure_dynamic_lds(k_rank_candidates<NDOF, NKEEP, WORLD>, kRankMaxLds, lds_opt_in); e != hipSuccess) return e;
   }
   const unsigned tiles = (unsigned)(((long long)a.m + a.tile_poses - 1) / a.tile_poses);
-  hipLaunchKernelGGL((k_rank_candidates<NDOF, NKEEP>), dim3(tiles, a.chunks), dim3(IKF_RANK_BLOCK), lds, s, a);
+  hipLaunchKernelGGL((k_rank_candidates<NDOF, NKEEP, WORLD>), dim3(tiles, a.chunks), dim3(IKF_RANK_BLOCK), lds, s, a);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   if (a.chunks > 1) hipLaunchKernelGGL((k_rank_merge<NDOF, NKEEP>), dim3((unsigned)(((long long)a.m + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -158,13 +174,21 @@ hipError_t launch_rank(int ndof, const RankArgs& a, hipStream_t s) {
   if (a.m <= 0) return hipSuccess;
   if (a.k < 1 || a.opt.n_keep < 1 || a.opt.n_keep > IKF_RANK_MAX_KEEP || a.opt.n_keep > a.k || a.chunks < 1 || a.per_chunk < 1 ||
       (long long)a.chunks * a.per_chunk < a.k || a.chunks > 65535 || a.tile_poses != rank_tile_poses(a.m) ||
-      (a.opt.reject_collisions && (!a.cm || a.cap_stride < 1 || a.cap_stride > IKF_MAX_CAPSULES * 6 + 1)) ||
+      ((a.opt.reject_collisions || a.world) && (!a.cm || a.cap_stride < 1 || a.cap_stride > IKF_MAX_CAPSULES * 6 + 1)) ||
       (a.chunks > 1 && (!a.part_score || !a.part_index || !a.part_count)))
     return hipErrorInvalidValue;
+  if (a.world) {
+    switch (rank_keep_capacity(a.opt.n_keep)) {
+      case 1: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, 1, true>(a, s))); break;
+      case 4: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, 4, true>(a, s))); break;
+      default: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, IKF_RANK_MAX_KEEP, true>(a, s))); break;
+    }
+    return hipErrorInvalidValue;
+  }
   switch (rank_keep_capacity(a.opt.n_keep)) {
-    case 1: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, 1>(a, s))); break;
-    case 4: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, 4>(a, s))); break;
-    default: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, IKF_RANK_MAX_KEEP>(a, s))); break;
+    case 1: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, 1, false>(a, s))); break;
+    case 4: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, 4, false>(a, s))); break;
+    default: IKF_NDOF_DISPATCH(ndof, return (launch_rank_as<ND, IKF_RANK_MAX_KEEP, false>(a, s))); break;
   }
   return hipErrorInvalidValue;
 }

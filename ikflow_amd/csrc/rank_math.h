@@ -78,6 +78,29 @@ IKF_HD float capsule_clearance(const Chain* __restrict__ ch, const CollisionMode
   return best;
 }
 
+// The chain walk of capsule_clearance alone: the world end points of every capsule into w (6 floats per capsule), the same arithmetic.  For
+// the world clearance (world_math.h) of a row whose self-collision walk did not run.
+template <int NDOF>
+IKF_HD void capsule_endpoints(const Chain* __restrict__ ch, const CollisionModel* __restrict__ cm, const float qv[NDOF], float* w) {
+  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, p[3] = {0.f, 0.f, 0.f};
+  const int nc = cm->n_caps;
+  for (int f = 0; f <= NDOF; ++f) {
+    if (f > 0) {
+      compose<float>(R, p, ch->joints[f - 1].pre);
+      apply_joint<float>(R, p, ch->joints[f - 1].kind, ch->joints[f - 1].axis, qv[f - 1]);
+    }
+    for (int c = 0; c < nc; ++c) {
+      if (cm->frame[c] != f) continue;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const float* pl = e == 0 ? cm->p0[c] : cm->p1[c];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) w[c * 6 + e * 3 + r] = R[3 * r + 0] * pl[0] + R[3 * r + 1] * pl[1] + R[3 * r + 2] * pl[2] + p[r];
+      }
+    }
+  }
+}
+
 IKF_HD float rank_inf() { return __builtin_huge_valf(); }
 
 // Score of one candidate row, +inf exactly when the row is inadmissible (include/ikflow_amd_rank.h).  q_ref: the pose's reference

@@ -346,6 +346,44 @@ class Engine:
             self._ck(self.lib.ikf_self_collision(self._h, q.data_ptr(), q.shape[0], dist.data_ptr(), col.data_ptr(), self._stream()))
         return dist, col.to(torch.bool)
 
+    # -- world collision (include/ikflow_amd_world.h) --------------------------------------------------------
+    def set_world(self, obstacles, min_clearance: float = 0.0) -> None:
+        """obstacles: a ikflow_amd.world.World, or [(kind, a[3], b[3], quat[4], radius)] in the layout of ikf_obstacle (an empty one clears).
+        While obstacles are set, rank_candidates / generate_ranked, path_search / generate_path and diverse_select / generate_diverse also
+        drop every candidate whose world clearance is below min_clearance.  Not while calls on this engine are in flight on another stream."""
+        obstacles = list(getattr(obstacles, "obstacles", obstacles))
+        if len(obstacles) > _lib.IKF_WORLD_MAX_OBSTACLES:
+            raise EngineError(f"a world holds at most {_lib.IKF_WORLD_MAX_OBSTACLES} obstacles, got {len(obstacles)}")
+        arr = (_lib.ikf_obstacle * max(len(obstacles), 1))()
+        for o, (kind, a, b, quat, radius) in zip(arr, obstacles):
+            o.kind, o.radius = int(kind), float(radius)
+            for k in range(3):
+                o.a[k], o.b[k] = float(a[k]), float(b[k])
+            for k in range(4):
+                o.quat[k] = float(quat[k])
+        self._ck(self.lib.ikf_set_world(self._h, arr, len(obstacles), float(min_clearance)))
+
+    def clear_world(self) -> None:
+        self._ck(self.lib.ikf_set_world(self._h, None, 0, 0.0))
+
+    @property
+    def world_size(self) -> int:
+        return int(self.lib.ikf_world_size(self._h))
+
+    def world_clearance(self, q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """[n x ndof] -> (signed clearance of the closest (capsule, obstacle) pair [n] f32 - 3.0e38 in an empty world -, that obstacle's index
+        [n] int32, that capsule's index [n] int32 (-1 in an empty world), clearance < the world's min_clearance [n] bool)."""
+        q = self._q(q)
+        n = q.shape[0]
+        dist = torch.empty(n, dtype=torch.float32, device=self.device)
+        obstacle = torch.empty(n, dtype=torch.int32, device=self.device)
+        capsule = torch.empty(n, dtype=torch.int32, device=self.device)
+        col = torch.empty(n, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_world_clearance(self._h, q.data_ptr(), n, dist.data_ptr(), obstacle.data_ptr(), capsule.data_ptr(),
+                                                  col.data_ptr(), self._stream()))
+        return dist, obstacle, capsule, col.to(torch.bool)
+
     # -- best-of-K ranking (include/ikflow_amd_rank.h) -----------------------------------------------------
     @property
     def has_collision_model(self) -> bool:

@@ -16,6 +16,7 @@ Differences, all documented in DESIGN.md:
 """
 from __future__ import annotations
 
+import math
 import pickle
 import warnings
 from time import time
@@ -128,6 +129,7 @@ class IKFlowSolver:
             warnings.warn("compile_model is ignored: the MI355X engine runs hand-written HIP kernels, nothing is traced.")
         self._model_weights_loaded = False
         self._engine = None  # created on first use, on the device of the inputs
+        self._world = None   # (World, min_clearance) of set_world: re-applied to every engine this solver creates
         # tests / tools only: "probes" binds lib/libikflow_amd_probes.so (the product + the priced-and-rejected forms of rounds 2 - 3);
         # set before the first call
         self.library_flavour = ""
@@ -174,8 +176,38 @@ class IKFlowSolver:
                     self._precision = "f32"
                     self._engine = eng
                     raise
+            if self._world is not None:
+                self._push_world(eng)
             self._engine = eng
         return self._engine
+
+    # -- the caller's scene --------------------------------------------------------------------------
+    def set_world(self, world, min_clearance: float = 0.0):
+        """Obstacles of the scene (ikflow_amd.world.World; None or an empty one: no scene).  While a world is set,
+        generate_ranked_ik_solutions, generate_ik_path and generate_diverse_ik_solutions also drop every candidate whose clearance from an
+        obstacle is below min_clearance - whatever reject_self_collisions says, which keeps meaning the robot against itself.  Needs the
+        robot's capsule model (Robot.set_collision_capsules)."""
+        from ikflow_amd.world import World
+
+        assert world is None or isinstance(world, World), f"world must be a ikflow_amd.world.World or None (got {type(world)})"
+        assert isinstance(min_clearance, (int, float)) and math.isfinite(min_clearance), f"min_clearance must be a finite number, got {min_clearance!r}"
+        if world is None or len(world) == 0:
+            self._world = None
+            if self._engine is not None:
+                self._engine.clear_world()
+            return
+        assert self._robot.has_collision_model, "set_world needs a collision model (Robot.set_collision_capsules)"
+        self._world = (world, float(min_clearance))
+        if self._engine is not None:
+            self._push_world(self._engine)
+        else:
+            self.engine()
+
+    def _push_world(self, eng):
+        if getattr(eng, "_collision_source", None) is not self._robot._collision_model:
+            eng.set_collision_model(*self._robot._collision_model)   # the solver's own handle, not the one Robot.config_self_collides uses
+            eng._collision_source = self._robot._collision_model
+        eng.set_world(*self._world)
 
     def set_precision(self, mode: str):
         """Arithmetic of the hidden Linear contractions: "f32" (exact f32 MFMA, default) or "f16x3" (error-compensated
@@ -320,7 +352,8 @@ class IKFlowSolver:
         ``pos_err + rot_weight * rot_err [+ ref_weight * ||q - q_ref[j]||]`` (metres; the default rot_weight is the ratio of
         generate_exact_ik_solutions' default thresholds, 1 mm / 0.1 rad).  Inadmissible: an error not below its threshold (when given), a
         joint strictly outside its limits (reject_joint_limits), a clearance below min_clearance (reject_self_collisions; None = when the
-        robot carries a capsule model).  Candidates are ordered by (score, sample index).
+        robot carries a capsule model).  A world set by set_world is in force: a candidate closer to an obstacle than the world's
+        min_clearance is inadmissible too.  Candidates are ordered by (score, sample index).
 
         Returns the named tuple (solutions [m x n_keep x ndof], scores [m x n_keep], repeat_index [m x n_keep] int32, n_admissible [m]
         int32[, row_scores [k * m]]); slots beyond a pose's admissible candidates hold 0 / +inf / -1."""
@@ -390,7 +423,7 @@ class IKFlowSolver:
         selection on the GPU without a host round trip (include/ikflow_amd_diverse.h).
 
         y: [7] or [m x 7]; 1 <= k <= 1024, 1 <= n_keep <= min(k, 16).  Latent layout, scores and admissibility are those of
-        generate_ranked_ik_solutions (without a reference configuration).  Slot 0 is that method's first choice; every later slot is the
+        generate_ranked_ik_solutions (without a reference configuration; a world set by set_world is in force).  Slot 0 is that method's first choice; every later slot is the
         admissible sample farthest (Euclidean in joint space, no angle wrapping; joint j scaled by a finite joint_weights[j] >= 0 when given) from
         the ones kept so far, ties to the lower sample index.  A pose's selection stops when no sample is left or the farthest one is
         closer than min_separation to a kept one: kept rows are pairwise at least min_separation apart, and when fewer than n_keep are
@@ -471,7 +504,7 @@ class IKFlowSolver:
         uses latent r at EVERY waypoint (the reference's visualizations.py oscillate_target(fixed_latent=True): under trained weights a fixed
         latent gives a solution that varies smoothly with the pose); otherwise as ``(k * T, dim)``, tile-major (row r * T + t is candidate r
         of waypoint t).  A candidate's node cost is ``pos_err + rot_weight * rot_err`` (metres), +inf when it is inadmissible (thresholds,
-        joint limits, self-collision as in generate_ranked_ik_solutions); the edge between consecutive candidates is their Euclidean joint
+        joint limits, self-collision and a world set by set_world as in generate_ranked_ik_solutions; nodes only, no swept test); the edge between consecutive candidates is their Euclidean joint
         distance (no angle wrapping), forbidden when a joint moves by more than max_joint_step.  The path minimises
         ``sum of edges + node_weight * sum of node costs`` (+ the edge from q_start to the first configuration when q_start is given); ties
         go to the lower candidate index.

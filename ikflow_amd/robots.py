@@ -328,6 +328,27 @@ class Robot:
         col = self._collision_engine(qq).self_collision(qq)[1]
         return bool(col[0].item()) if single else col
 
+    # -- the caller's scene (jrl.Robot's environment queries; the obstacle kinds and clearances are ikflow_amd.world's) ---------
+    def env_collision_distances(self, q, world):
+        """[n x ndof], a ikflow_amd.world.World -> [n] signed clearance of the closest (capsule, obstacle) pair (negative = penetrating;
+        3.0e38 in an empty world).  Needs the capsule model, like self_collision_distances."""
+        return self._world_query(q, world, 0.0)[0]
+
+    def config_collides_with_env(self, q, world, min_clearance=0.0):
+        """[n x ndof] -> [n] bool: closer to an obstacle of `world` than min_clearance (one configuration [ndof] -> Python bool)."""
+        single = getattr(q, "ndim", 2) == 1
+        qq = q.reshape(1, -1) if single else q
+        col = self._world_query(qq, world, min_clearance)[3]
+        return bool(col[0].item()) if single else col
+
+    def _world_query(self, q, world, min_clearance):
+        eng = self._collision_engine(q)
+        eng.set_world(world, min_clearance)
+        try:
+            return eng.world_clearance(q)
+        finally:
+            eng.clear_world()   # the kinematics engine is shared: its selection calls must not inherit this scene
+
 
 _HALF_PI = math.pi / 2.0
 
