@@ -135,14 +135,14 @@ extern "C" void ikf_destroy(ikf_model* m) {
   if (m->d_blin) (void)hipFree(m->d_blin);
   if (m->d_chain) (void)hipFree(m->d_chain);
   if (m->d_collision) (void)hipFree(m->d_collision);
-  if (m->rk_q) (void)hipFree(m->rk_q);
-  if (m->rk_part_score) (void)hipFree(m->rk_part_score);
-  if (m->rk_part_index) (void)hipFree(m->rk_part_index);
-  if (m->rk_part_count) (void)hipFree(m->rk_part_count);
-  if (m->pt_node) (void)hipFree(m->pt_node);
-  if (m->pt_bp) (void)hipFree(m->pt_bp);
-  if (m->pt_latent) (void)hipFree(m->pt_latent);
-  if (m->dv_score) (void)hipFree(m->dv_score);
+  m->rk_q.release();
+  m->rk_part_score.release();
+  m->rk_part_index.release();
+  m->rk_part_count.release();
+  m->pt_node.release();
+  m->pt_bp.release();
+  m->pt_latent.release();
+  m->dv_score.release();
   if (m->d_world) (void)hipFree(m->d_world);
   if (m->ex_count) (void)hipFree(m->ex_count);
   if (m->h_count) (void)hipHostFree(m->h_count);

@@ -1,6 +1,6 @@
 // C-ABI of libikflow_amd.so, world collision (include/ikflow_amd_world.h): the caller's obstacles as state of the handle, validated and normalised
 // on the host, and the per-row clearance query (k_world_clearance, world_kernels.hip).  What the obstacles do to the selection entry points is
-// rank_args_world (api_rank.hip).
+// in score_candidates (api_rank.hip).
 #include "ikf_model.h"
 
 static bool all_finite(const float* v, int n) {

@@ -43,6 +43,28 @@ struct DeviceGuard {
   if (dev_guard_.err != hipSuccess)                                                                            \
     return fail(IKF_ERR_HIP, std::string("hipSetDevice failed: ") + hipGetErrorString(dev_guard_.err));
 
+// A device array that only grows (the candidate stage's buffers).  ensure(n): nothing when it already holds n elements; otherwise the old
+// array is freed BEFORE the new one is allocated, and a failed hipMalloc leaves it empty - nothing leaked, no dangling pointer.  No destructor:
+// the handle's buffers are released by ikf_destroy, under its DeviceGuard.
+template <class T>
+struct DeviceBuf {
+  T* p = nullptr;
+  long long cap = 0;  // elements
+  hipError_t ensure(long long n) {
+    if (n <= cap) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc(&p, sizeof(T) * (size_t)n);
+    if (e == hipSuccess) cap = n;
+    else p = nullptr;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
 struct ikf_model {
   int device = 0;
   // the per-handle scratch is shared by all calls: a call that arrives on a different stream than the previous one
@@ -176,19 +198,16 @@ struct ikf_model {
   int* h_count = nullptr;         // pinned host
   // best-of-K ranking scratch (api_rank.hip): the flow's candidate rows and the K-chunks' partial lists
   int n_caps = 0;                 // capsules of d_collision (sizes the ranking kernel's LDS)
-  long long rk_rows = 0, rk_lists = 0;
-  float* rk_q = nullptr;          // [rows][ndof]
-  float* rk_part_score = nullptr; // [lists][IKF_RANK_MAX_KEEP]
-  int* rk_part_index = nullptr;   // [lists][IKF_RANK_MAX_KEEP]
-  int* rk_part_count = nullptr;   // [lists]
+  DeviceBuf<float> rk_q;          // [rows][ndof]
+  DeviceBuf<float> rk_part_score; // [lists][IKF_RANK_MAX_KEEP]   (the three part_* arrays are grown together, from one list count)
+  DeviceBuf<int> rk_part_index;   // [lists][IKF_RANK_MAX_KEEP]
+  DeviceBuf<int> rk_part_count;   // [lists]
   // path IK scratch (api_path.hip; the candidate rows are rk_q): node costs and back-pointers of the lattice, the shared latent expanded
-  long long pt_rows = 0, pt_latent_rows = 0;
-  float* pt_node = nullptr;       // [rows]
-  uint8_t* pt_bp = nullptr;       // [rows] a byte per node (+ padding: path_bp_bytes)
-  float* pt_latent = nullptr;     // [latent rows][D]
+  DeviceBuf<float> pt_node;       // [rows]
+  DeviceBuf<uint8_t> pt_bp;       // [rows] a byte per node (+ padding: path_bp_bytes)
+  DeviceBuf<float> pt_latent;     // [latent rows][D]
   // diverse-of-K scratch (api_diverse.hip; the candidate rows are rk_q, the partial lists the ranking's): the row scores
-  long long dv_rows = 0;
-  float* dv_score = nullptr;      // [rows]
+  DeviceBuf<float> dv_score;      // [rows]
   // world collision (api_world.hip): the caller's obstacles; with world_n > 0 the ranking kernel also rejects rows closer than world_min_clearance
   WorldModel* d_world = nullptr;  // allocated by the first ikf_set_world with obstacles
   int world_n = 0;
@@ -280,8 +299,34 @@ ikf_status build_split_weights(ikf_model* m);
 ikf_status build_frag_weights(ikf_model* m);
 ikf_status check_ready(ikf_model* m, const char* fn);
 ikf_status run_flow_guarded(ikf_model* m, PoseSource ps, const float* d_latent, long long rows, int clamp_limits, float* d_q_out, hipStream_t s);
-ikf_status ensure_rank_rows(ikf_model* m, long long rows);
-ikf_status ensure_rank_lists(ikf_model* m, long long poses);
-void rank_args_world(const ikf_model* m, RankArgs* a);   // the handle's world into a->world / world_min_clearance (and the capsule slices it needs)
+// The candidate stage of ranked / path / diverse IK (api_rank.hip): k candidates per pose, tile-major, scored by k_rank_candidates.
+ikf_status ensure_rank_rows(ikf_model* m, long long rows);   // the candidate rows rk_q
+// The checks the six entries share once the handle is there, in this order: options, count >= 0 (named `count`: "n_poses" / "T"), k in
+// 1 .. k_max (0: no upper limit), the family's own rule (`rule_fault`: what to report, or null), k * count, reject_collisions without a
+// collision model, then the empty call (*nothing_to_do) and, last, null device pointers (`have_pointers`: the family's required ones).
+ikf_status check_candidates(const ikf_model* m, const std::string& who, const char* count, int64_t n, int k, int k_max, const void* opt,
+                            bool reject_collisions, const char* rule_fault, bool have_pointers, bool* nothing_to_do);
+// The flow on k tiled candidates per pose (latent [k * n][D]; the conditional of row r * n + j is pose j) into rk_q, which the caller has sized.
+ikf_status flow_candidates(ikf_model* m, const float* d_poses, int64_t n, int k, const float* d_latent, int clamp_to_limits, hipStream_t s);
+// The one place that fills a RankArgs and launches the ranking kernel: chunking, capsule slices, the handle's world, the partial lists.
+ikf_status score_candidates(ikf_model* m, const float* d_poses, int64_t n, int k, const float* d_q, const float* d_q_ref,
+                            const ikf_rank_options& opt, float* d_q_out, float* d_score_out, int32_t* d_index_out, int32_t* d_count_out,
+                            float* d_row_score, hipStream_t s);
+// Path and diverse score with the ranking's rule: n_keep = 1, no reference configuration, their six scoring fields as they are.
+template <class Opt>
+inline ikf_rank_options scoring_options(const Opt& o) {
+  ikf_rank_options r{};
+  r.n_keep = 1;
+  r.rot_weight = o.rot_weight;
+  r.max_pos_err = o.max_pos_err;
+  r.max_rot_err = o.max_rot_err;
+  r.reject_limits = o.reject_limits;
+  r.reject_collisions = o.reject_collisions;
+  r.min_clearance = o.min_clearance;
+  return r;
+}
+// What ikf_reserve_ranked / _path / _diverse share: the argument test (`rule`: the family's message), candidate rows, partial lists and,
+// with weights loaded, the flow's own reservation.
+ikf_status reserve_candidates(ikf_model* m, const char* who, const char* rule, int64_t max_poses, int max_k, int k_max);
 }  // namespace ikf
 #pragma GCC visibility pop

@@ -90,6 +90,13 @@ def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _scoring_fields(rot_weight, max_pos_err, max_rot_err, reject_limits, reject_collisions, min_clearance) -> dict:
+    """The six fields that ikf_rank_options, ikf_path_options and ikf_diverse_options share: no bound is -1, switches are 0 / 1."""
+    return dict(rot_weight=float(rot_weight), max_pos_err=-1.0 if max_pos_err is None else float(max_pos_err),
+                max_rot_err=-1.0 if max_rot_err is None else float(max_rot_err), reject_limits=1 if reject_limits else 0,
+                reject_collisions=1 if reject_collisions else 0, min_clearance=float(min_clearance))
+
+
 class Engine:
     """One ikf_model handle on one device."""
 
@@ -401,10 +408,8 @@ class Engine:
     def rank_options(n_keep: int = 1, rot_weight: float = 0.01, ref_weight: float = 0.0, max_pos_err: Optional[float] = None,
                      max_rot_err: Optional[float] = None, reject_limits: bool = True, reject_collisions: bool = False,
                      min_clearance: float = 0.0) -> "_lib.ikf_rank_options":
-        return _lib.ikf_rank_options(
-            int(n_keep), float(rot_weight), float(ref_weight), -1.0 if max_pos_err is None else float(max_pos_err),
-            -1.0 if max_rot_err is None else float(max_rot_err), 1 if reject_limits else 0, 1 if reject_collisions else 0, float(min_clearance),
-        )
+        return _lib.ikf_rank_options(n_keep=int(n_keep), ref_weight=float(ref_weight), **_scoring_fields(
+            rot_weight, max_pos_err, max_rot_err, reject_limits, reject_collisions, min_clearance))
 
     def _rank_outputs(self, m: int, k: int, n_keep: int, row_scores: bool):
         q_out = torch.empty((m, n_keep, self.layout.ndof), dtype=torch.float32, device=self.device)
@@ -414,17 +419,25 @@ class Engine:
         rows = torch.empty((k * m,), dtype=torch.float32, device=self.device) if row_scores else None
         return q_out, score, index, count, rows
 
-    def _rank_inputs(self, target_poses: torch.Tensor, k: int, rows: torch.Tensor, cols: int, q_ref: Optional[torch.Tensor], opt, what: str):
+    def _candidate_inputs(self, target_poses: torch.Tensor, k: int, rows: torch.Tensor, cols: int, what: str, opt, max_k: Optional[int],
+                          max_keep: int, extra: Optional[torch.Tensor], extra_name: str, per_pose: bool):
+        """What rank_candidates / generate_ranked and diverse_select / generate_diverse check alike: the poses, k against the family's limit
+        (None: none), the tile-major rows, the family's optional tensor (q_ref per pose, joint_weights per joint) and n_keep."""
         tp = self._on_device(target_poses, "target_poses")
         assert tp.ndim == 2 and tp.shape[1] == 7, f"target_poses must be of shape [m x 7], got {tuple(tp.shape)}"
+        assert max_k is None or 1 <= k <= max_k, f"k must be in 1 .. {max_k}, got {k}"
         m = tp.shape[0]
         rows = self._on_device(rows, what)
         assert rows.ndim == 2 and rows.shape == (k * m, cols), f"{what} must be [{k * m} x {cols}] (tile-major), got {tuple(rows.shape)}"
-        if q_ref is not None:
-            q_ref = self._on_device(q_ref, "q_ref")
-            assert q_ref.shape == (m, self.layout.ndof), f"q_ref must be [{m} x {self.layout.ndof}], got {tuple(q_ref.shape)}"
-        assert 1 <= opt.n_keep <= min(k, _lib.IKF_RANK_MAX_KEEP), f"n_keep must be in 1 .. min(k, {_lib.IKF_RANK_MAX_KEEP}), got {opt.n_keep}"
-        return tp, m, rows, q_ref
+        if extra is not None:
+            extra = self._on_device(extra, extra_name)
+            shape = (m, self.layout.ndof) if per_pose else (self.layout.ndof,)
+            assert extra.shape == shape, f"{extra_name} must be [{' x '.join(map(str, shape))}], got {tuple(extra.shape)}"
+        assert 1 <= opt.n_keep <= min(k, max_keep), f"n_keep must be in 1 .. min(k, {max_keep}), got {opt.n_keep}"
+        return tp, m, rows, extra
+
+    def _rank_inputs(self, target_poses: torch.Tensor, k: int, rows: torch.Tensor, cols: int, q_ref: Optional[torch.Tensor], opt, what: str):
+        return self._candidate_inputs(target_poses, k, rows, cols, what, opt, None, _lib.IKF_RANK_MAX_KEEP, q_ref, "q_ref", True)
 
     def rank_candidates(self, target_poses: torch.Tensor, k: int, q: torch.Tensor, opt, q_ref: Optional[torch.Tensor] = None,
                         row_scores: bool = False):
@@ -460,10 +473,8 @@ class Engine:
                      reject_limits: bool = True, reject_collisions: bool = False, min_clearance: float = 0.0, node_weight: float = 1.0,
                      max_joint_step: Optional[float] = None) -> "_lib.ikf_path_options":
         return _lib.ikf_path_options(
-            float(rot_weight), -1.0 if max_pos_err is None else float(max_pos_err), -1.0 if max_rot_err is None else float(max_rot_err),
-            1 if reject_limits else 0, 1 if reject_collisions else 0, float(min_clearance), float(node_weight),
-            -1.0 if max_joint_step is None else float(max_joint_step),
-        )
+            node_weight=float(node_weight), max_joint_step=-1.0 if max_joint_step is None else float(max_joint_step),
+            **_scoring_fields(rot_weight, max_pos_err, max_rot_err, reject_limits, reject_collisions, min_clearance))
 
     def _path_inputs(self, waypoints: torch.Tensor, k: int, rows: torch.Tensor, shared: bool, cols: int, q_start: Optional[torch.Tensor], what: str):
         wp = self._on_device(waypoints, "waypoints")
@@ -518,23 +529,12 @@ class Engine:
     def diverse_options(n_keep: int = 1, rot_weight: float = 0.01, max_pos_err: Optional[float] = None, max_rot_err: Optional[float] = None,
                         reject_limits: bool = True, reject_collisions: bool = False, min_clearance: float = 0.0,
                         min_separation: float = 0.0) -> "_lib.ikf_diverse_options":
-        return _lib.ikf_diverse_options(
-            int(n_keep), float(rot_weight), -1.0 if max_pos_err is None else float(max_pos_err), -1.0 if max_rot_err is None else float(max_rot_err),
-            1 if reject_limits else 0, 1 if reject_collisions else 0, float(min_clearance), float(min_separation),
-        )
+        return _lib.ikf_diverse_options(n_keep=int(n_keep), min_separation=float(min_separation), **_scoring_fields(
+            rot_weight, max_pos_err, max_rot_err, reject_limits, reject_collisions, min_clearance))
 
     def _diverse_inputs(self, target_poses: torch.Tensor, k: int, rows: torch.Tensor, cols: int, joint_weights: Optional[torch.Tensor], opt, what: str):
-        tp = self._on_device(target_poses, "target_poses")
-        assert tp.ndim == 2 and tp.shape[1] == 7, f"target_poses must be of shape [m x 7], got {tuple(tp.shape)}"
-        assert 1 <= k <= _lib.IKF_DIVERSE_MAX_K, f"k must be in 1 .. {_lib.IKF_DIVERSE_MAX_K}, got {k}"
-        m = tp.shape[0]
-        rows = self._on_device(rows, what)
-        assert rows.ndim == 2 and rows.shape == (k * m, cols), f"{what} must be [{k * m} x {cols}] (tile-major), got {tuple(rows.shape)}"
-        if joint_weights is not None:
-            joint_weights = self._on_device(joint_weights, "joint_weights")
-            assert joint_weights.shape == (self.layout.ndof,), f"joint_weights must be [{self.layout.ndof}], got {tuple(joint_weights.shape)}"
-        assert 1 <= opt.n_keep <= min(k, _lib.IKF_DIVERSE_MAX_KEEP), f"n_keep must be in 1 .. min(k, {_lib.IKF_DIVERSE_MAX_KEEP}), got {opt.n_keep}"
-        return tp, m, rows, joint_weights
+        return self._candidate_inputs(target_poses, k, rows, cols, what, opt, _lib.IKF_DIVERSE_MAX_K, _lib.IKF_DIVERSE_MAX_KEEP, joint_weights,
+                                      "joint_weights", False)
 
     def _diverse_outputs(self, m: int, k: int, n_keep: int, row_scores: bool):
         q_out = torch.empty((m, n_keep, self.layout.ndof), dtype=torch.float32, device=self.device)

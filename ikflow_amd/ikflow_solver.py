@@ -324,6 +324,52 @@ class IKFlowSolver:
             return solutions, valids
         return out
 
+    # -- what the three candidate-consuming methods below share -----------------------------------------------------
+    def _candidate_args(self, poses, name: str, count: str, k, k_max: Optional[int], latent, shared_latent: bool, latent_distribution,
+                        latent_scale, reject_self_collisions: Optional[bool], pos_error_threshold, rot_error_threshold):
+        """The asserts generate_ranked_ik_solutions, generate_diverse_ik_solutions and generate_ik_path have in common, before any device
+        work.  `name` / `count`: what the poses are called ("y" / "m": one pose [7] is accepted too; "waypoints" / "T").
+        -> (poses [count x 7], count, latent rows, reject_self_collisions resolved)"""
+        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
+        assert isinstance(poses, torch.Tensor), f"{name} must be a torch.Tensor (got {type(poses)})."
+        if count == "m":
+            assert poses.numel() == 7 or (poses.ndim == 2 and poses.shape[1] == 7), f"{name} must be of shape [7] or [m x 7], got {tuple(poses.shape)}"
+        else:
+            assert poses.ndim == 2 and poses.shape[1] == 7, f"{name} must be of shape [{count} x 7], got {tuple(poses.shape)}"
+        if k_max is None:
+            assert isinstance(k, int) and k > 0, f"k must be a positive int, got {k!r}"
+        else:
+            assert isinstance(k, int) and 1 <= k <= k_max, f"k must be an int in 1 .. {k_max}, got {k!r}"
+        assert isinstance(latent_distribution, str)
+        assert isinstance(latent_scale, float)
+        assert isinstance(latent, torch.Tensor) or latent is None, f"latent must either be a torch.Tensor or None (got {type(latent)})."
+        if reject_self_collisions is None:
+            reject_self_collisions = self._robot.has_collision_model
+        assert not reject_self_collisions or self._robot.has_collision_model, (
+            "reject_self_collisions needs a collision model (Robot.set_collision_capsules)")
+        poses2 = poses.reshape(1, 7) if poses.numel() == 7 and count == "m" else poses
+        n = poses2.shape[0]
+        assert k * n <= 2 ** 31 - 1, f"k * {count} must be at most 2^31 - 1, got {k * n}"
+        assert pos_error_threshold is None or pos_error_threshold >= 0, "pos_error_threshold must be None (no bound) or >= 0"
+        assert rot_error_threshold is None or rot_error_threshold >= 0, "rot_error_threshold must be None (no bound) or >= 0"
+        n_latent = k if shared_latent else k * n
+        assert latent is None or tuple(latent.shape) == (n_latent, self._network_width), (
+            f"latent must be [{n_latent} x {self._network_width}], got {tuple(latent.shape) if latent is not None else None}")
+        if "cuda" in str(config.DEVICE):
+            assert "cpu" not in str(poses.device), f"Cuda is available ('{config.DEVICE}'), but target_poses are on {poses.device}"
+        return poses2, n, n_latent, reject_self_collisions
+
+    def _candidate_engine(self, device, reject_self_collisions: bool, latent, latent_distribution, latent_scale, n_latent: int):
+        """-> (the engine of that device, with the robot's capsule model pushed when collisions are rejected; the latent, drawn when None)"""
+        eng = self.engine(device)
+        if reject_self_collisions and getattr(eng, "_collision_source", None) is not self._robot._collision_model:
+            # the solver's own handle, not the one Robot.config_self_collides uses
+            eng.set_collision_model(*self._robot._collision_model)
+            eng._collision_source = self._robot._collision_model
+        if latent is None:
+            latent = draw_latent(latent_distribution, latent_scale, (n_latent, self._network_width), device)
+        return eng, latent
+
     # -- best of K samples per pose ------------------------------------------------------------------------------
     def generate_ranked_ik_solutions(
         self,
@@ -357,38 +403,14 @@ class IKFlowSolver:
 
         Returns the named tuple (solutions [m x n_keep x ndof], scores [m x n_keep], repeat_index [m x n_keep] int32, n_admissible [m]
         int32[, row_scores [k * m]]); slots beyond a pose's admissible candidates hold 0 / +inf / -1."""
-        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
-        assert isinstance(y, torch.Tensor), f"y must be a torch.Tensor (got {type(y)})."
-        assert y.numel() == 7 or (y.ndim == 2 and y.shape[1] == 7), f"y must be of shape [7] or [m x 7], got {tuple(y.shape)}"
-        assert isinstance(k, int) and k > 0, f"k must be a positive int, got {k!r}"
+        y2, m, n_latent, reject_self_collisions = self._candidate_args(
+            y, "y", "m", k, None, latent, False, latent_distribution, latent_scale, reject_self_collisions, pos_error_threshold, rot_error_threshold)
         assert isinstance(n_keep, int) and 1 <= n_keep <= min(k, 16), f"n_keep must be in 1 .. min(k, 16), got {n_keep!r}"
-        assert isinstance(latent_distribution, str)
-        assert isinstance(latent_scale, float)
-        assert isinstance(latent, torch.Tensor) or latent is None, f"latent must either be a torch.Tensor or None (got {type(latent)})."
-        if reject_self_collisions is None:
-            reject_self_collisions = self._robot.has_collision_model
-        assert not reject_self_collisions or self._robot.has_collision_model, (
-            "reject_self_collisions needs a collision model (Robot.set_collision_capsules)")
-        y2 = y.reshape(1, 7) if y.numel() == 7 else y
-        m = y2.shape[0]
-        assert k * m <= 2 ** 31 - 1, f"k * m must be at most 2^31 - 1, got {k * m}"
         assert q_ref is None or (isinstance(q_ref, torch.Tensor) and (tuple(q_ref.shape) == (m, self.ndof) or (m == 1 and tuple(q_ref.shape) == (self.ndof,)))), (
             f"q_ref must be [{m} x {self.ndof}], got {tuple(q_ref.shape) if isinstance(q_ref, torch.Tensor) else type(q_ref)}")
-        assert pos_error_threshold is None or pos_error_threshold >= 0, "pos_error_threshold must be None (no bound) or >= 0"
-        assert rot_error_threshold is None or rot_error_threshold >= 0, "rot_error_threshold must be None (no bound) or >= 0"
-        assert latent is None or tuple(latent.shape) == (k * m, self._network_width), (
-            f"latent must be [{k * m} x {self._network_width}], got {tuple(latent.shape) if latent is not None else None}")
-        if "cuda" in str(config.DEVICE):
-            assert "cpu" not in str(y.device), f"Cuda is available ('{config.DEVICE}'), but target_poses are on {y.device}"
 
         with torch.inference_mode():
-            eng = self.engine(y.device)
-            if reject_self_collisions and getattr(eng, "_collision_source", None) is not self._robot._collision_model:
-                # the solver's own handle, not the one Robot.config_self_collides uses
-                eng.set_collision_model(*self._robot._collision_model)
-                eng._collision_source = self._robot._collision_model
-            if latent is None:
-                latent = draw_latent(latent_distribution, latent_scale, (k * m, self._network_width), y.device)
+            eng, latent = self._candidate_engine(y.device, reject_self_collisions, latent, latent_distribution, latent_scale, n_latent)
             opt = eng.rank_options(n_keep, rot_weight, ref_weight, pos_error_threshold, rot_error_threshold, reject_joint_limits,
                                    reject_self_collisions, min_clearance)
             ref = None if q_ref is None else q_ref.reshape(m, self.ndof)
@@ -431,41 +453,17 @@ class IKFlowSolver:
 
         Returns the named tuple (solutions [m x n_keep x ndof], scores, repeat_index int32, separation [all m x n_keep], n_kept [m] int32,
         n_admissible [m] int32[, row_scores [k * m]]); unfilled slots hold 0 / +inf / -1 / +inf."""
-        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
-        assert isinstance(y, torch.Tensor), f"y must be a torch.Tensor (got {type(y)})."
-        assert y.numel() == 7 or (y.ndim == 2 and y.shape[1] == 7), f"y must be of shape [7] or [m x 7], got {tuple(y.shape)}"
-        assert isinstance(k, int) and 1 <= k <= 1024, f"k must be an int in 1 .. 1024, got {k!r}"
+        y2, m, n_latent, reject_self_collisions = self._candidate_args(
+            y, "y", "m", k, 1024, latent, False, latent_distribution, latent_scale, reject_self_collisions, pos_error_threshold, rot_error_threshold)
         assert isinstance(n_keep, int) and 1 <= n_keep <= min(k, 16), f"n_keep must be in 1 .. min(k, 16), got {n_keep!r}"
         assert isinstance(min_separation, (int, float)) and min_separation >= 0, f"min_separation must be >= 0, got {min_separation!r}"
-        assert isinstance(latent_distribution, str)
-        assert isinstance(latent_scale, float)
-        assert isinstance(latent, torch.Tensor) or latent is None, f"latent must either be a torch.Tensor or None (got {type(latent)})."
-        if reject_self_collisions is None:
-            reject_self_collisions = self._robot.has_collision_model
-        assert not reject_self_collisions or self._robot.has_collision_model, (
-            "reject_self_collisions needs a collision model (Robot.set_collision_capsules)")
-        y2 = y.reshape(1, 7) if y.numel() == 7 else y
-        m = y2.shape[0]
-        assert k * m <= 2 ** 31 - 1, f"k * m must be at most 2^31 - 1, got {k * m}"
         assert joint_weights is None or (isinstance(joint_weights, torch.Tensor) and tuple(joint_weights.shape) == (self.ndof,)), (
             f"joint_weights must be [{self.ndof}], got {tuple(joint_weights.shape) if isinstance(joint_weights, torch.Tensor) else type(joint_weights)}")
         assert joint_weights is None or bool((torch.isfinite(joint_weights) & (joint_weights >= 0)).all().item()), (
             "joint_weights must all be finite and >= 0")
-        assert pos_error_threshold is None or pos_error_threshold >= 0, "pos_error_threshold must be None (no bound) or >= 0"
-        assert rot_error_threshold is None or rot_error_threshold >= 0, "rot_error_threshold must be None (no bound) or >= 0"
-        assert latent is None or tuple(latent.shape) == (k * m, self._network_width), (
-            f"latent must be [{k * m} x {self._network_width}], got {tuple(latent.shape) if latent is not None else None}")
-        if "cuda" in str(config.DEVICE):
-            assert "cpu" not in str(y.device), f"Cuda is available ('{config.DEVICE}'), but target_poses are on {y.device}"
 
         with torch.inference_mode():
-            eng = self.engine(y.device)
-            if reject_self_collisions and getattr(eng, "_collision_source", None) is not self._robot._collision_model:
-                # the solver's own handle, not the one Robot.config_self_collides uses
-                eng.set_collision_model(*self._robot._collision_model)
-                eng._collision_source = self._robot._collision_model
-            if latent is None:
-                latent = draw_latent(latent_distribution, latent_scale, (k * m, self._network_width), y.device)
+            eng, latent = self._candidate_engine(y.device, reject_self_collisions, latent, latent_distribution, latent_scale, n_latent)
             opt = eng.diverse_options(n_keep, rot_weight, pos_error_threshold, rot_error_threshold, reject_joint_limits,
                                       reject_self_collisions, min_clearance, min_separation)
             w = None if joint_weights is None else joint_weights.to(device=y.device, dtype=torch.float32)
@@ -514,40 +512,17 @@ class IKFlowSolver:
 
         Returns the named tuple (path [T x ndof], index [T] int32, cost, n_reachable [T] int32[, node_costs [k * T]]); without an admissible
         path: rows 0, indices -1, cost +inf, and n_reachable shows the first waypoint nothing reaches."""
-        assert self._model_weights_loaded, "Model weights have not been loaded. Call load_state_dict(...)"
-        assert isinstance(waypoints, torch.Tensor), f"waypoints must be a torch.Tensor (got {type(waypoints)})."
-        assert waypoints.ndim == 2 and waypoints.shape[1] == 7, f"waypoints must be of shape [T x 7], got {tuple(waypoints.shape)}"
-        assert isinstance(k, int) and 1 <= k <= 256, f"k must be an int in 1 .. 256, got {k!r}"
-        assert isinstance(latent_distribution, str)
-        assert isinstance(latent_scale, float)
-        assert isinstance(latent, torch.Tensor) or latent is None, f"latent must either be a torch.Tensor or None (got {type(latent)})."
+        waypoints, T, n_latent, reject_self_collisions = self._candidate_args(
+            waypoints, "waypoints", "T", k, 256, latent, shared_latent, latent_distribution, latent_scale, reject_self_collisions,
+            pos_error_threshold, rot_error_threshold)
         assert isinstance(refine_steps, int) and refine_steps >= 0, f"refine_steps must be an int >= 0, got {refine_steps!r}"
-        if reject_self_collisions is None:
-            reject_self_collisions = self._robot.has_collision_model
-        assert not reject_self_collisions or self._robot.has_collision_model, (
-            "reject_self_collisions needs a collision model (Robot.set_collision_capsules)")
-        T = waypoints.shape[0]
-        assert k * T <= 2 ** 31 - 1, f"k * T must be at most 2^31 - 1, got {k * T}"
         assert q_start is None or (isinstance(q_start, torch.Tensor) and tuple(q_start.shape) == (self.ndof,)), (
             f"q_start must be [{self.ndof}], got {tuple(q_start.shape) if isinstance(q_start, torch.Tensor) else type(q_start)}")
-        assert pos_error_threshold is None or pos_error_threshold >= 0, "pos_error_threshold must be None (no bound) or >= 0"
-        assert rot_error_threshold is None or rot_error_threshold >= 0, "rot_error_threshold must be None (no bound) or >= 0"
         assert node_weight >= 0, f"node_weight must be >= 0, got {node_weight!r}"
         assert max_joint_step is None or max_joint_step >= 0, "max_joint_step must be None (no gate) or >= 0"
-        n_latent = k if shared_latent else k * T
-        assert latent is None or tuple(latent.shape) == (n_latent, self._network_width), (
-            f"latent must be [{n_latent} x {self._network_width}], got {tuple(latent.shape) if latent is not None else None}")
-        if "cuda" in str(config.DEVICE):
-            assert "cpu" not in str(waypoints.device), f"Cuda is available ('{config.DEVICE}'), but target_poses are on {waypoints.device}"
 
         with torch.inference_mode():
-            eng = self.engine(waypoints.device)
-            if reject_self_collisions and getattr(eng, "_collision_source", None) is not self._robot._collision_model:
-                # the solver's own handle, not the one Robot.config_self_collides uses
-                eng.set_collision_model(*self._robot._collision_model)
-                eng._collision_source = self._robot._collision_model
-            if latent is None:
-                latent = draw_latent(latent_distribution, latent_scale, (n_latent, self._network_width), waypoints.device)
+            eng, latent = self._candidate_engine(waypoints.device, reject_self_collisions, latent, latent_distribution, latent_scale, n_latent)
             opt = eng.path_options(rot_weight, pos_error_threshold, rot_error_threshold, reject_joint_limits, reject_self_collisions,
                                    min_clearance, node_weight, max_joint_step)
             path, index, cost, reach, nodes = eng.generate_path(waypoints, k, latent, shared_latent, clamp_to_joint_limits, opt,

@@ -6,13 +6,10 @@ import itertools
 
 import numpy as np
 
+from helpers import same_bits  # noqa: F401  (used as DH.same_bits)
+
 F = np.float32
 INF = F(np.inf)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def dist2_f32(a, b, w=None):

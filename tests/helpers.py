@@ -16,6 +16,12 @@ from oracle.robot_tables import OracleRobot
 from oracle.robot_tables import robot as oracle_robot_by_name
 
 
+def same_bits(a, b):
+    """Same shape, dtype and bytes: equality that tells -0.0 from 0.0 and one NaN from another."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
 def O(robot) -> OracleRobot:
     """The oracle's own description of `robot` (looked up by name only)."""
     return robot if isinstance(robot, OracleRobot) else oracle_robot_by_name(robot if isinstance(robot, str) else robot.name)

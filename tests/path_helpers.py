@@ -7,6 +7,8 @@ import re
 
 import numpy as np
 
+from helpers import same_bits  # noqa: F401  (used as PH.same_bits)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 INF = F(np.inf)
@@ -85,11 +87,6 @@ def brute_force_f64(q, node, T, k, q_start=None, node_weight=1.0, max_step=None)
         if total < best:
             best, best_idx = total, np.array(idx, np.int32)
     return best_idx, best
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def random_lattice(T, k, nd, seed, spread=0.3):

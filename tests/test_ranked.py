@@ -94,20 +94,15 @@ def _rank(eng, poses, q, k, opt, q_ref=None, stream=None, null=(), latent=None, 
     return out
 
 
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.int32), b.view(np.int32))
-
-
 def _check_selection(out, q, m, k, n_keep, what=""):
     """The returned lists against the stable lexsort of the engine's own row scores of each pose - no tolerance."""
     idx, sc, cnt = RH.select(out["row_score"], m, k, n_keep)
     assert np.array_equal(out["index"], idx), f"{what}: index_out is not the lexsort of the row scores, first pose {np.flatnonzero((out['index'] != idx).any(1))[:3]}"
-    assert _same_bits(out["score"], sc), f"{what}: score_out"
+    assert H.same_bits(out["score"], sc), f"{what}: score_out"
     assert np.array_equal(out["count"], cnt), f"{what}: count_out"
     qn = q.numpy().reshape(k, m, -1)
     want_q = np.where((idx >= 0)[..., None], qn[np.maximum(idx, 0), np.arange(m)[:, None]], np.float32(0.0))
-    assert _same_bits(out["q_out"], want_q.astype(np.float32)), f"{what}: q_out is not the candidate rows at index_out"
+    assert H.same_bits(out["q_out"], want_q.astype(np.float32)), f"{what}: q_out is not the candidate rows at index_out"
     assert np.isposinf(out["score"][idx < 0]).all() and (out["q_out"][idx < 0] == 0).all()
 
 
@@ -216,9 +211,9 @@ def test_a_pose_ranked_alone_equals_the_pose_inside_a_batch(k):
     q3 = q.reshape(k, m, -1)
     for j in (0, 128, 256):
         alone = _rank(eng, poses[j:j + 1], q3[:, j].contiguous(), k, opt, q_ref[j:j + 1])
-        assert _same_bits(alone["row_score"], full["row_score"].reshape(k, m)[:, j]), j
+        assert H.same_bits(alone["row_score"], full["row_score"].reshape(k, m)[:, j]), j
         for n in ("score", "index", "q_out"):
-            assert _same_bits(alone[n][0], full[n][j]), (n, j)
+            assert H.same_bits(alone[n][0], full[n][j]), (n, j)
         assert alone["count"][0] == full["count"][j]
 
 
@@ -232,11 +227,11 @@ def test_permuting_a_poses_candidates_permutes_the_indices():
     perm = torch.randperm(k, generator=torch.Generator().manual_seed(1))
     b = _rank(eng, poses, q.reshape(k, m, -1)[perm].reshape(k * m, -1).contiguous(), k, opt)
     back = np.where(b["index"] >= 0, perm.numpy()[np.maximum(b["index"], 0)], -1)
-    assert _same_bits(a["score"], b["score"]) and np.array_equal(a["count"], b["count"])
+    assert H.same_bits(a["score"], b["score"]) and np.array_equal(a["count"], b["count"])
     rs = a["row_score"].reshape(k, m)
     distinct = np.array([len(np.unique(rs[:, j][np.isfinite(rs[:, j])])) == np.isfinite(rs[:, j]).sum() for j in range(m)])
     assert distinct.mean() >= 0.9                                       # (without ties the order is the scores' alone, so it must carry over exactly)
-    assert np.array_equal(back[distinct], a["index"][distinct]) and _same_bits(a["q_out"][distinct], b["q_out"][distinct])
+    assert np.array_equal(back[distinct], a["index"][distinct]) and H.same_bits(a["q_out"][distinct], b["q_out"][distinct])
     for j in np.flatnonzero(~distinct):                                 # (with a tie the index decides: the same scores, perhaps other rows)
         assert len(set(back[j].tolist())) == len(set(a["index"][j].tolist()))
 
@@ -250,12 +245,12 @@ def test_non_default_stream_and_null_outputs():
         opt = _opt(n_keep=4, max_pos=0.05)
         ref = _rank(eng, poses, q, k, opt)
         got = _rank(eng, poses, q, k, opt, stream=torch.cuda.Stream(device=DEV))
-        assert all(_same_bits(ref[n], got[n]) for n in OUTPUTS)
+        assert all(H.same_bits(ref[n], got[n]) for n in OUTPUTS)
         for null in OUTPUTS[1:]:
             got = _rank(eng, poses, q, k, opt, null=(null,))
-            assert null not in got and all(_same_bits(ref[n], got[n]) for n in got)
+            assert null not in got and all(H.same_bits(ref[n], got[n]) for n in got)
         got = _rank(eng, poses, q, k, opt, null=OUTPUTS[1:])
-        assert _same_bits(ref["q_out"], got["q_out"])
+        assert H.same_bits(ref["q_out"], got["q_out"])
 
 
 def test_status_codes():
@@ -461,4 +456,66 @@ def test_after_reserve_ranked_a_call_of_that_size_allocates_nothing():
     assert free0 - free1 <= grown_by_torch, f"the engine allocated {free0 - free1 - grown_by_torch} bytes after ikf_reserve_ranked"
     fresh = Engine(s.layout, robot, DEV)
     fresh.load_state_dict(s._state_dict_np)
-    assert all(_same_bits(full[n], v) for n, v in run(fresh, m, k).items())   # (the reservation changes no result)
+    assert all(H.same_bits(full[n], v) for n, v in run(fresh, m, k).items())   # (the reservation changes no result)
+
+
+# ---- 7. the grow-only buffers of the candidate stage, shared by ranked / path / diverse IK --------------------------------------------------
+def test_candidate_buffers_regrow_across_families_and_are_released_with_the_handle():
+    """One engine takes, for ranked, path and diverse IK in turn, a small call (m = 3, k = 5: one chunk), then one that regrows every buffer of
+    the candidate stage and uses the partial lists (m = 70, k = 130), then the small call again - interleaved, so the candidate rows and lists
+    one family grew are what the next one finds.  Every result has the bits of the same call on a fresh engine.  Path IK runs without node costs
+    and with a shared latent, diverse-of-K without row scores, so the handle's own node, back-pointer, latent and score arrays are in use.
+    Then the engine goes, and the device's free memory (the accounting of the three reserve tests) is back to what it was before the engine was
+    created, up to what torch's own cache grew.  That baseline is taken after the fresh engines of the references are gone: what the runtime
+    loads once, with the first launch of a kernel, is not the engine's."""
+    import gc
+
+    from ikflow_amd.engine import Engine
+
+    s, robot, lay, sd = _solver("tiny")
+    sizes = [(3, 5), (70, 130), (3, 5)]
+    _, poses = H.reachable_poses(robot, 70, 3)
+    poses = poses.float().to(DEV)
+    L = H.latents(130 * 70, lay.dim, 5).to(DEV)
+
+    def engine():
+        eng = Engine(s.layout, robot, DEV)
+        eng.load_state_dict(s._state_dict_np)
+        return eng
+
+    def ranked(eng, m, k):
+        return eng.generate_ranked(poses[:m], k, L[:k * m], True, eng.rank_options(n_keep=4, reject_limits=True), row_scores=True)
+
+    def path(eng, m, k):
+        return eng.generate_path(poses[:m], k, L[:k], True, True, eng.path_options(reject_limits=True))
+
+    def diverse(eng, m, k):
+        return eng.generate_diverse(poses[:m], k, L[:k * m], True, eng.diverse_options(n_keep=4, min_separation=0.05))
+
+    def bits(outs):
+        torch.cuda.synchronize()
+        return [None if t is None else t.cpu().numpy() for t in outs]
+
+    families = (ranked, path, diverse)
+    want = {}
+    for call in families:
+        for m, k in sizes[:2]:
+            fresh = engine()
+            want[call, m, k] = bits(call(fresh, m, k))
+            del fresh
+    gc.collect()
+    torch.cuda.synchronize()
+    free0, stat0 = torch.cuda.mem_get_info(DEV)[0], torch.cuda.memory_reserved(DEV)
+    eng = engine()
+    assert eng.rank_chunks(3, 5) == 1 and eng.rank_chunks(70, 130) > 1
+    for m, k in sizes:
+        for call in families:
+            got = bits(call(eng, m, k))
+            assert len(got) == len(want[call, m, k])
+            for i, (g, w) in enumerate(zip(got, want[call, m, k])):
+                assert (g is None and w is None) or H.same_bits(g, w), f"{call.__name__} m={m} k={k}: output {i} differs from a fresh engine's"
+    del eng
+    gc.collect()
+    torch.cuda.synchronize()
+    free1, stat1 = torch.cuda.mem_get_info(DEV)[0], torch.cuda.memory_reserved(DEV)
+    assert free0 - free1 <= stat1 - stat0, f"{free0 - free1 - (stat1 - stat0)} bytes of device memory did not come back with the handle"

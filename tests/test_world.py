@@ -18,7 +18,7 @@ import rank_helpers as RH
 import world_helpers as WH
 from ikflow_amd import _lib
 from ikflow_amd.world import World
-from test_ranked import _check_selection, _opt, _rank, _same_bits
+from test_ranked import _check_selection, _opt, _rank
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -202,15 +202,15 @@ def test_clearing_the_world_and_a_far_world_give_the_call_without_a_world_bit_fo
         during = _rank(eng, poses, q, k, opt, q_ref)
         assert np.isposinf(during["row_score"]).sum() > np.isposinf(before["row_score"]).sum()
         both = np.isfinite(during["row_score"])
-        assert _same_bits(during["row_score"][both], before["row_score"][both])   # (an admitted row keeps its score)
+        assert H.same_bits(during["row_score"][both], before["row_score"][both])   # (an admitted row keeps its score)
         eng.clear_world()
         after = _rank(eng, poses, q, k, opt, q_ref)
-        assert all(_same_bits(after[n], before[n]) for n in before)
+        assert all(H.same_bits(after[n], before[n]) for n in before)
         far = WH.far_world()
         eng.set_world(far, 1.0)
         assert eng.world_size == len(far) and float(eng.world_clearance(q.to(DEV))[0].min()) > 1.0
         distant = _rank(eng, poses, q, k, opt, q_ref)
-        assert all(_same_bits(distant[n], before[n]) for n in before)
+        assert all(H.same_bits(distant[n], before[n]) for n in before)
 
 
 # ---- 5. path IK and diverse-of-K -----------------------------------------------------------------------------------------------------------------
@@ -307,20 +307,20 @@ def test_generate_ranked_with_a_world_equals_the_flow_then_rank_candidates():
     opt = eng.rank_options(n_keep, mm_to_m(1) / 0.1, 0.0, None, None, True, False, 0.0)
     two_step = eng.rank_candidates(y, k, q, opt, row_scores=True)
     for a, b in zip(got, two_step):
-        assert _same_bits(a.cpu().numpy(), b.cpu().numpy())
+        assert H.same_bits(a.cpu().numpy(), b.cpu().numpy())
     n_inf, n_inf_without = int(torch.isinf(got.row_scores).sum()), int(torch.isinf(without.row_scores).sum())
     assert n_inf_without < n_inf < k * m
     far_rows = torch.isinf(got.row_scores) & ~torch.isinf(without.row_scores)
     assert bool((eng.world_clearance(q)[0][far_rows] < thr + 1e-5).all())
     one = s.generate_ranked_ik_solutions(y, k, 1, latent=L, reject_self_collisions=False, return_row_scores=True)
     div = s.generate_diverse_ik_solutions(y, k, n_keep, latent=L, reject_self_collisions=False, return_row_scores=True)
-    assert _same_bits(div.row_scores.cpu().numpy(), one.row_scores.cpu().numpy())   # (the score stage of diverse-of-K is the ranking with n_keep = 1)
+    assert H.same_bits(div.row_scores.cpu().numpy(), one.row_scores.cpu().numpy())   # (the score stage of diverse-of-K is the ranking with n_keep = 1)
     assert np.array_equal(np.isinf(one.row_scores.cpu().numpy()), np.isinf(got.row_scores.cpu().numpy()))
     s.set_world(None)
     assert eng.world_size == 0
     again = s.generate_ranked_ik_solutions(y, k, n_keep, latent=L, reject_self_collisions=False, return_row_scores=True)
     for a, b in zip(again, without):
-        assert _same_bits(a.cpu().numpy(), b.cpu().numpy())
+        assert H.same_bits(a.cpu().numpy(), b.cpu().numpy())
 
 
 # ---- 7. two handles --------------------------------------------------------------------------------------------------------------------------------
@@ -335,11 +335,11 @@ def test_a_world_on_one_handle_does_not_change_another():
     poses, q, _, cl, thr = WH.rank_case(which, m, k)
     opt = _opt(n_keep=2)
     before_a, before_b = _rank(eng, poses, q, k, opt), _rank(other, poses, q, k, opt)
-    assert all(_same_bits(before_a[n], before_b[n]) for n in before_a)
+    assert all(H.same_bits(before_a[n], before_b[n]) for n in before_a)
     eng.set_world(WH.scene(which, WH.RANK_SCENE), thr)
     assert eng.world_size == 7 and other.world_size == 0
     after_a, after_b = _rank(eng, poses, q, k, opt), _rank(other, poses, q, k, opt)
-    assert all(_same_bits(after_b[n], before_b[n]) for n in before_b)
+    assert all(H.same_bits(after_b[n], before_b[n]) for n in before_b)
     assert np.isposinf(after_a["row_score"]).sum() > np.isposinf(before_a["row_score"]).sum()
     assert (_clearance(other, q)["clearance"] == np.float32(3.0e38)).all()
 
