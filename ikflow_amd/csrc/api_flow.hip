@@ -17,10 +17,10 @@ static int pick_variant(const ikf_model* m, long long rows) {
 // flow inverse pass over `rows` rows (chunked); replaces nn_model(latent, c=cond, rev=True) + slice + clamp
 // ---------------------------------------------------------------------------------------------------------------
 static const float* chain_lo(const ikf_model* m) {
-  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(m->d_chain) + offsetof(Chain, lo));
+  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(m->d_chain.p) + offsetof(Chain, lo));
 }
 static const float* chain_hi(const ikf_model* m) {
-  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(m->d_chain) + offsetof(Chain, hi));
+  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(m->d_chain.p) + offsetof(Chain, hi));
 }
 
 // fn(r0, nr) for consecutive pieces of at most `piece` rows of [r_base, r_base + rows); stops at the first status that is not IKF_OK
@@ -66,13 +66,12 @@ static ikf_status chain_census(ikf_model* m, hipStream_t s) {
   hipDeviceProp_t prop{};
   IKF_HIP(hipGetDeviceProperties(&prop, m->device));
   if (prop.multiProcessorCount != IKF_CHAIN_XCDS * IKF_CHAIN_PER_XCD) return IKF_OK;
-  unsigned* d_out = nullptr;
-  IKF_HIP(hipMalloc(&d_out, sizeof(unsigned) * 256));
+  DeviceBuf<unsigned> d_out;
+  IKF_HIP(d_out.ensure(256));
   hipError_t e = launch_xcd_census(d_out, s);
   unsigned h[256];
   if (e == hipSuccess) e = hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(d_out);
   IKF_HIP(e);
   int per[16] = {};
   for (int b = 0; b < 256; ++b) per[h[b] & 15]++;
@@ -568,7 +567,7 @@ static ikf_status run_flow_cluster(ikf_model* m, int G, const PoseSource& ps, co
   const bool local = m->cl_local != 0 && cluster_local_form(G) && cluster_grid(c.n_rt, G, true) <= (unsigned)m->n_cu;
   c.give_up = m->h_cl_give_up;
   if (tagged) {
-    unsigned* const abort_t = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(m->cl_sync_t) + m->cl_sync_t_bytes - 128);
+    unsigned* const abort_t = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(m->cl_sync_t.p) + m->cl_sync_t_bytes - 128);
     if (m->cl_tag_dirty) {
       IKF_HIP(cluster_tagged_init(m->cl_xbuf_t, cluster_xbuf_floats((int)(m->cl_rows / IKF_RO_ROWS)), m->cl_sync_t, m->cl_sync_t_bytes - 128, abort_t, s));
       m->cl_tag_dirty = false;
@@ -580,7 +579,7 @@ static ikf_status run_flow_cluster(ikf_model* m, int G, const PoseSource& ps, co
     c.test_far = local ? m->cl_far_next : 0;   // (variant 191: honoured by the tagged form's placement check too)
     if (local) m->cl_far_next = 0;
     // the members' placement words sit behind the partial sums of the largest launch (the epoch-word form's flag area, unused here)
-    c.xcc_words = reinterpret_cast<unsigned*>(m->cl_sync_t) + (size_t)(m->cl_rows / IKF_RO_ROWS) * 8 * 256;
+    c.xcc_words = reinterpret_cast<unsigned*>(m->cl_sync_t.p) + (size_t)(m->cl_rows / IKF_RO_ROWS) * 8 * 256;
     m->cl_launch_seq = (m->cl_launch_seq + 1) & 0xffffffu;
     if (m->cl_launch_seq == 0xffffffu) m->cl_launch_seq = 0;
     c.launch_seq = m->cl_launch_seq;
@@ -590,7 +589,7 @@ static ikf_status run_flow_cluster(ikf_model* m, int G, const PoseSource& ps, co
   } else {
     c.xbuf = m->cl_xbuf;
     c.pbuf = m->cl_sync;
-    c.flags = reinterpret_cast<unsigned*>(m->cl_sync) + (size_t)c.n_rt * G * 256;
+    c.flags = reinterpret_cast<unsigned*>(m->cl_sync.p) + (size_t)c.n_rt * G * 256;
     c.abort_word = c.flags + (size_t)c.n_rt * G * 32;
     c.test_far = local ? m->cl_far_next : 0;
     if (local) m->cl_far_next = 0;

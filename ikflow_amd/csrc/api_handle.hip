@@ -1,6 +1,7 @@
 // C-ABI of libikflow_amd.so, the handle: ikf_last_error, ikf_create / ikf_destroy, the scratch allocators (ensure_*, ikf_reserve*) and
 // every setting, getter and profiling hook that only reads or writes the handle.  See include/ikflow_amd.h for the contract.
 #include "ikf_model.h"
+#include <cassert>
 
 static thread_local std::string g_last_error;
 
@@ -15,24 +16,14 @@ extern "C" const char* ikf_dominant_kernel_name(void) { return fused_kernel_name
 extern "C" const char* ikf_split_kernel_name(void) { return split_kernel_name(); }
 
 static void free_scratch(ikf_model* m) {
-  if (m->xbuf) (void)hipFree(m->xbuf);
-  if (m->hA) (void)hipFree(m->hA);
-  if (m->hB) (void)hipFree(m->hB);
-  if (m->xbuf2) (void)hipFree(m->xbuf2);
-  if (m->pbuf) (void)hipFree(m->pbuf);
-  m->xbuf = m->hA = m->hB = m->xbuf2 = m->pbuf = m->pbuf_alt = nullptr;
+  m->xbuf.release();
+  m->hA.release();
+  m->hB.release();
+  m->xbuf2.release();
+  m->pbuf.release();
+  m->pbuf_alt = nullptr;
   m->chunk_rows = 0;
   m->chain_tab_valid = false;  // (the table holds these pointers)
-}
-static void free_exact(ikf_model* m) {
-  if (m->ex_q) (void)hipFree(m->ex_q);
-  if (m->ex_row_valid) (void)hipFree(m->ex_row_valid);
-  if (m->ex_pose_idx) (void)hipFree(m->ex_pose_idx);
-  if (m->ex_block_scratch) (void)hipFree(m->ex_block_scratch);
-  if (m->ex_pose_first) (void)hipFree(m->ex_pose_first);
-  m->ex_q = nullptr; m->ex_row_valid = nullptr; m->ex_pose_idx = nullptr;
-  m->ex_block_scratch = nullptr; m->ex_pose_first = nullptr;
-  m->exact_rows = m->exact_poses = 0;
 }
 
 extern "C" ikf_status ikf_create(const ikf_model_desc* desc, int device, ikf_model** out) {
@@ -87,22 +78,22 @@ extern "C" ikf_status ikf_create(const ikf_model_desc* desc, int device, ikf_mod
     }
   }
   memcpy(ch.tool, desc->tool, sizeof(ch.tool));
-  hipError_t e = hipMalloc(&m->d_chain, sizeof(Chain));
+  hipError_t e = m->d_chain.ensure(1);
   if (e == hipSuccess) e = hipMemcpy(m->d_chain, &ch, sizeof(Chain), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&m->ex_count, sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc(&m->h_count, sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&m->d_split_flag, sizeof(int));
+  if (e == hipSuccess) e = m->ex_count.ensure(1);
+  if (e == hipSuccess) e = m->h_count.alloc(1);
+  if (e == hipSuccess) e = m->d_split_flag.ensure(1);
   if (e == hipSuccess) e = hipMemset(m->d_split_flag, 0, sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc(&m->h_split_flag, sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&m->d_arrive, sizeof(unsigned) * kArriveWords);
+  if (e == hipSuccess) e = m->h_split_flag.alloc(1);
+  if (e == hipSuccess) e = m->d_arrive.ensure(kArriveWords);
   if (e == hipSuccess) e = hipMemset(m->d_arrive, 0, sizeof(unsigned) * kArriveWords);
-  if (e == hipSuccess) e = hipHostMalloc(&m->h_give_up, sizeof(int), hipHostMallocMapped);
+  if (e == hipSuccess) e = m->h_give_up.alloc(1, hipHostMallocMapped);
   if (e == hipSuccess) *m->h_give_up = 0;
-  if (e == hipSuccess) e = hipHostMalloc(&m->h_cl_give_up, sizeof(int), hipHostMallocMapped);
+  if (e == hipSuccess) e = m->h_cl_give_up.alloc(1, hipHostMallocMapped);
   if (e == hipSuccess) *m->h_cl_give_up = 0;
-  if (e == hipSuccess) e = hipMalloc(&m->d_chain_ctl, sizeof(unsigned) * IKF_CHAIN_CTL_WORDS);
+  if (e == hipSuccess) e = m->d_chain_ctl.ensure(IKF_CHAIN_CTL_WORDS);
   if (e == hipSuccess) e = hipMemset(m->d_chain_ctl, 0, sizeof(unsigned) * IKF_CHAIN_CTL_WORDS);
-  if (e == hipSuccess) e = hipMalloc(&m->d_chain_tab, sizeof(ChainSubnet) * 2 * (size_t)desc->nb_nodes);
+  if (e == hipSuccess) e = m->d_chain_tab.ensure(2 * (long long)desc->nb_nodes);
   if (e != hipSuccess) {
     ikf_destroy(m);
     return fail(IKF_ERR_HIP, std::string("ikf_create: allocation failed: ") + hipGetErrorString(e));
@@ -114,47 +105,9 @@ extern "C" ikf_status ikf_create(const ikf_model_desc* desc, int device, ikf_mod
 extern "C" void ikf_destroy(ikf_model* m) {
   if (!m) return;
   DeviceGuard dev_guard_(m->device);
-  free_scratch(m);
-  free_exact(m);
-  if (m->arena) (void)hipFree(m->arena);
-  if (m->split_arena) (void)hipFree(m->split_arena);
-  if (m->split_frag_arena) (void)hipFree(m->split_frag_arena);
-  if (m->wfrag_arena) (void)hipFree(m->wfrag_arena);
-  if (m->ro_stream) (void)hipFree(m->ro_stream);
-  if (m->d_ro_sub) (void)hipFree(m->d_ro_sub);
-  if (m->d_ro_sub_fwd) (void)hipFree(m->d_ro_sub_fwd);
-  if (m->cl_xbuf) (void)hipFree(m->cl_xbuf);
-  if (m->cl_sync) (void)hipFree(m->cl_sync);
-  if (m->cl_xbuf_t) (void)hipFree(m->cl_xbuf_t);
-  if (m->cl_sync_t) (void)hipFree(m->cl_sync_t);
-  if (m->h_cl_give_up) (void)hipHostFree(m->h_cl_give_up);
-  if (m->d_perm_inv) (void)hipFree(m->d_perm_inv);
-  if (m->d_Minv) (void)hipFree(m->d_Minv);
-  if (m->d_M) (void)hipFree(m->d_M);
-  if (m->d_perm) (void)hipFree(m->d_perm);
-  if (m->d_blin) (void)hipFree(m->d_blin);
-  if (m->d_chain) (void)hipFree(m->d_chain);
-  if (m->d_collision) (void)hipFree(m->d_collision);
-  m->rk_q.release();
-  m->rk_part_score.release();
-  m->rk_part_index.release();
-  m->rk_part_count.release();
-  m->pt_node.release();
-  m->pt_bp.release();
-  m->pt_latent.release();
-  m->dv_score.release();
-  if (m->d_world) (void)hipFree(m->d_world);
-  if (m->ex_count) (void)hipFree(m->ex_count);
-  if (m->h_count) (void)hipHostFree(m->h_count);
-  if (m->d_split_flag) (void)hipFree(m->d_split_flag);
-  if (m->h_split_flag) (void)hipHostFree(m->h_split_flag);
-  if (m->d_arrive) (void)hipFree(m->d_arrive);
-  if (m->h_give_up) (void)hipHostFree(m->h_give_up);
-  if (m->d_chain_ctl) (void)hipFree(m->d_chain_ctl);
-  if (m->d_chain_tab) (void)hipFree(m->d_chain_tab);
   for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
   if (m->tail_event) (void)hipEventDestroy(m->tail_event);
-  delete m;
+  delete m;  // (every buffer is a DeviceBuf / PinnedBuf member: freed here, on the handle's device)
 }
 
 extern "C" int ikf_weights_loaded(const ikf_model* m) { return (m && m->loaded) ? 1 : 0; }
@@ -173,10 +126,10 @@ ikf_status ikf::ensure_scratch(ikf_model* m, long long rows) {
   want = (want + 127) / 128 * 128;  // the contraction kernels store whole 128-row tiles (no row predicate)
   if (want <= m->chunk_rows) return IKF_OK;
   free_scratch(m);
-  IKF_HIP(hipMalloc(&m->xbuf, sizeof(float) * (size_t)want * m->dims.D));
-  IKF_HIP(hipMalloc(&m->hA, sizeof(float) * (size_t)want * m->dims.width));
-  IKF_HIP(hipMalloc(&m->hB, sizeof(float) * (size_t)want * m->dims.width));
-  IKF_HIP(hipMalloc(&m->xbuf2, sizeof(float) * (size_t)want * m->dims.D));
+  IKF_HIP(m->xbuf.ensure(want * m->dims.D));
+  IKF_HIP(m->hA.ensure(want * m->dims.width));
+  IKF_HIP(m->hB.ensure(want * m->dims.width));
+  IKF_HIP(m->xbuf2.ensure(want * m->dims.D));
   const size_t slots = (size_t)(fused_max_slots(m->dims.width) > 0 ? fused_max_slots(m->dims.width) : 1);
   // With ONE hidden contraction per subnet (coeff_fn_config 2, e.g. TINY_MODEL_PARAMS) the one-launch subnet head (k_entry_gemm_skinny*) is
   // also the subnet's LAST contraction: the same launch reads the previous subnet's partial sums (pending coupling, every slot of its row
@@ -185,7 +138,7 @@ ikf_status ikf::ensure_scratch(ikf_model* m, long long rows) {
   // red two-ranks-on-one-GPU test of round 5, tools/two_tenant_determinism.py).  Such shapes alternate between two sets by subnet parity.
   const size_t pset = slots * (size_t)want * IKF_PSTRIDE;
   const bool two_sets = m->dims.n_hidden == 2;
-  IKF_HIP(hipMalloc(&m->pbuf, sizeof(float) * pset * (two_sets ? 2 : 1)));
+  IKF_HIP(m->pbuf.ensure((long long)(pset * (two_sets ? 2 : 1))));
   m->pbuf_alt = two_sets ? m->pbuf + pset : m->pbuf;
   m->chunk_rows = want;
   return IKF_OK;
@@ -196,25 +149,23 @@ ikf_status ikf::ensure_scratch(ikf_model* m, long long rows) {
 // (right after the round's count has been read, i.e. with the stream idle) without touching the active-pose list.
 static ikf_status ensure_exact_poses(ikf_model* m, long long poses) {
   if (poses <= m->exact_poses) return IKF_OK;
-  if (m->ex_pose_idx) (void)hipFree(m->ex_pose_idx);
-  if (m->ex_block_scratch) (void)hipFree(m->ex_block_scratch);
-  if (m->ex_pose_first) (void)hipFree(m->ex_pose_first);
-  m->ex_pose_idx = nullptr; m->ex_block_scratch = nullptr; m->ex_pose_first = nullptr;
+  m->ex_pose_idx.release();
+  m->ex_block_scratch.release();
+  m->ex_pose_first.release();
   m->exact_poses = 0;
-  IKF_HIP(hipMalloc(&m->ex_pose_idx, sizeof(int) * (size_t)poses));
-  IKF_HIP(hipMalloc(&m->ex_pose_first, sizeof(unsigned) * (size_t)poses));
-  IKF_HIP(hipMalloc(&m->ex_block_scratch, sizeof(int) * 2 * (size_t)(compact_blocks(poses) + 1)));
+  IKF_HIP(m->ex_pose_idx.ensure(poses));
+  IKF_HIP(m->ex_pose_first.ensure(poses));
+  IKF_HIP(m->ex_block_scratch.ensure(2 * (long long)(compact_blocks(poses) + 1)));
   m->exact_poses = poses;
   return IKF_OK;
 }
 ikf_status ikf::ensure_exact_rows(ikf_model* m, long long rows) {
   if (rows <= m->exact_rows) return IKF_OK;
-  if (m->ex_q) (void)hipFree(m->ex_q);
-  if (m->ex_row_valid) (void)hipFree(m->ex_row_valid);
-  m->ex_q = nullptr; m->ex_row_valid = nullptr;
+  m->ex_q.release();
+  m->ex_row_valid.release();
   m->exact_rows = 0;
-  IKF_HIP(hipMalloc(&m->ex_q, sizeof(float) * (size_t)rows * m->dims.ndof));
-  IKF_HIP(hipMalloc(&m->ex_row_valid, (size_t)rows));
+  IKF_HIP(m->ex_q.ensure(rows * m->dims.ndof));
+  IKF_HIP(m->ex_row_valid.ensure(rows));
   m->exact_rows = rows;
   return IKF_OK;
 }
@@ -235,19 +186,21 @@ extern "C" ikf_status ikf_reserve_exact(ikf_model* m, int64_t max_poses, int max
 
 ikf_status ikf::ensure_cluster_scratch(ikf_model* m, long long rows) {
   if (rows <= m->cl_rows) return IKF_OK;
-  if (m->cl_xbuf) (void)hipFree(m->cl_xbuf);
-  if (m->cl_sync) (void)hipFree(m->cl_sync);
-  if (m->cl_xbuf_t) (void)hipFree(m->cl_xbuf_t);
-  if (m->cl_sync_t) (void)hipFree(m->cl_sync_t);
-  m->cl_xbuf = nullptr; m->cl_sync = nullptr; m->cl_xbuf_t = nullptr; m->cl_sync_t = nullptr; m->cl_rows = 0;
+  m->cl_xbuf.release();
+  m->cl_sync.release();
+  m->cl_xbuf_t.release();
+  m->cl_sync_t.release();
+  m->cl_rows = 0;
   const long long cap = (long long)m->n_cu / 2 * IKF_RO_ROWS;   // the largest chunk the form takes (G = 2)
   const int tiles = (int)((cap + IKF_RO_ROWS - 1) / IKF_RO_ROWS);
-  IKF_HIP(hipMalloc(&m->cl_xbuf, sizeof(float) * cluster_xbuf_floats(tiles)));
-  IKF_HIP(hipMalloc(&m->cl_sync, cluster_sync_bytes(tiles, 8)));   // (sized for G = 8 on every tile: 4.6 KB per tile)
+  const size_t sync_bytes = cluster_sync_bytes(tiles, 8);   // (sized for G = 8 on every tile: 4.6 KB per tile)
+  assert(sync_bytes % sizeof(float) == 0);   // (cl_sync / cl_sync_t are float arrays sized in bytes: whole words by construction)
+  IKF_HIP(m->cl_xbuf.ensure((long long)cluster_xbuf_floats(tiles)));
+  IKF_HIP(m->cl_sync.ensure((long long)(sync_bytes / sizeof(float))));
   // the tagged hand-over's own pair (same sizes; its abort word is the block's LAST word, wherever a launch's partial sums end)
-  m->cl_sync_t_bytes = cluster_sync_bytes(tiles, 8);
-  IKF_HIP(hipMalloc(&m->cl_xbuf_t, sizeof(float) * cluster_xbuf_floats(tiles)));
-  IKF_HIP(hipMalloc(&m->cl_sync_t, m->cl_sync_t_bytes));
+  m->cl_sync_t_bytes = sync_bytes;
+  IKF_HIP(m->cl_xbuf_t.ensure((long long)cluster_xbuf_floats(tiles)));
+  IKF_HIP(m->cl_sync_t.ensure((long long)(sync_bytes / sizeof(float))));
   m->cl_tag_dirty = true;   // (created by the first launch that uses them, on its stream)
   m->cl_rows = cap;
   return IKF_OK;

@@ -74,7 +74,7 @@ extern "C" ikf_status ikf_set_collision_model(ikf_model* m, const ikf_capsule* h
     cm.pair_b[k] = (uint8_t)b;
   }
   IKF_ON_DEVICE(m)
-  if (!m->d_collision) IKF_HIP(hipMalloc(&m->d_collision, sizeof(CollisionModel)));
+  IKF_HIP(m->d_collision.ensure(1));
   IKF_HIP(hipMemcpy(m->d_collision, &cm, sizeof(CollisionModel), hipMemcpyHostToDevice));
   m->n_caps = n_capsules;
   return IKF_OK;

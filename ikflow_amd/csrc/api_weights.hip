@@ -44,7 +44,7 @@ ikf_status ikf::build_split_weights(ikf_model* m) {
   IKF_HIP(hipDeviceSynchronize());
   IKF_HIP(hipMemcpy(&pending_flag, m->d_split_flag, sizeof(int), hipMemcpyDeviceToHost));
   IKF_HIP(hipMemset(m->d_split_flag, 0, sizeof(int)));
-  IKF_HIP(hipMalloc(&m->split_arena, sizeof(uint16_t) * per * n_layers));
+  IKF_HIP(m->split_arena.ensure((long long)(per * n_layers)));
   m->w_mid_split.assign((size_t)2 * NB * 3, nullptr);
   size_t li = 0;
   for (int si = 0; si < 2 * NB; ++si)
@@ -57,7 +57,7 @@ ikf_status ikf::build_split_weights(ikf_model* m) {
   m->w_mid_split_frag.assign((size_t)2 * NB * 3, nullptr);
   if (split_cfg_needs_frag(split_pick_cfg(1, W))) {
     const size_t per_f = (size_t)W * W;  // dwords
-    IKF_HIP(hipMalloc(&m->split_frag_arena, sizeof(float) * per_f * n_layers));
+    IKF_HIP(m->split_frag_arena.ensure((long long)(per_f * n_layers)));
     li = 0;
     for (int si = 0; si < 2 * NB; ++si)
       for (int l = 0; l < d.n_hidden - 1; ++l, ++li) {
@@ -72,8 +72,8 @@ ikf_status ikf::build_split_weights(ikf_model* m) {
   IKF_HIP(hipMemcpy(&wflag, m->d_split_flag, sizeof(int), hipMemcpyDeviceToHost));
   IKF_HIP(hipMemcpy(m->d_split_flag, &pending_flag, sizeof(int), hipMemcpyHostToDevice));
   if (wflag != 0) {
-    (void)hipFree(m->split_arena); m->split_arena = nullptr;
-    if (m->split_frag_arena) { (void)hipFree(m->split_frag_arena); m->split_frag_arena = nullptr; }
+    m->split_arena.release();
+    m->split_frag_arena.release();
     m->w_mid_split.assign((size_t)2 * NB * 3, nullptr);
     m->w_mid_split_frag.assign((size_t)2 * NB * 3, nullptr);
     m->precision = 0;
@@ -85,7 +85,7 @@ ikf_status ikf::build_split_weights(ikf_model* m) {
 // fragment-major images (k_wfrag_pack) of every hidden Linear weight for k_flow_gemm_skinny (rows <= 512): the second
 // copy costs width^2 * 4 B per layer (201 MB for the Panda model) of the 288 GB
 static void drop_frag_weights(ikf_model* m) {
-  if (m->wfrag_arena) { (void)hipFree(m->wfrag_arena); m->wfrag_arena = nullptr; }
+  m->wfrag_arena.release();
   m->w_mid_frag.assign((size_t)2 * m->desc.nb_nodes * 3, nullptr);
   m->wfrag_built = false;
 }
@@ -99,7 +99,7 @@ ikf_status ikf::build_frag_weights(ikf_model* m) {
   if (d.n_hidden < 2 || fused_pick_cfg(512, W) != fused_skinny_cfg()) return IKF_OK;
   const size_t per = (size_t)W * W;
   const size_t n_layers = (size_t)2 * NB * (d.n_hidden - 1);
-  IKF_HIP(hipMalloc(&m->wfrag_arena, sizeof(float) * per * n_layers));
+  IKF_HIP(m->wfrag_arena.ensure((long long)(per * n_layers)));
   size_t li = 0;
   for (int si = 0; si < 2 * NB; ++si)
     for (int l = 0; l < d.n_hidden - 1; ++l, ++li) {
@@ -116,9 +116,9 @@ ikf_status ikf::build_frag_weights(ikf_model* m) {
 // the row-owner kernel's parameter stream: every subnet's weights in execution order (block NB-1 .. 0, s1 then s2) and, inside a subnet,
 // in the order the kernel consumes them (k_rowowner_pack), plus the small per-subnet table (last-Linear bias, perm_inv, split)
 static void drop_rowowner_stream(ikf_model* m) {
-  if (m->ro_stream) { (void)hipFree(m->ro_stream); m->ro_stream = nullptr; }
-  if (m->d_ro_sub) { (void)hipFree(m->d_ro_sub); m->d_ro_sub = nullptr; }
-  if (m->d_ro_sub_fwd) { (void)hipFree(m->d_ro_sub_fwd); m->d_ro_sub_fwd = nullptr; }
+  m->ro_stream.release();
+  m->d_ro_sub.release();
+  m->d_ro_sub_fwd.release();
 }
 // The forward pass walks the same stream with the subnets in reverse order (k_flow_rowowner_fwd, ro_fwd_offset); its table lists them in
 // forward execution order (block 0 .. NB-1, subnet 2 then subnet 1).  PermuteRandom forward of block b + 1 rides on block b's subnet-1 entry
@@ -141,10 +141,10 @@ static hipError_t build_rowowner_stream_hip(ikf_model* m, const std::vector<int>
   const FlowDims& d = m->dims;
   const int NB = m->desc.nb_nodes, n_sub = 2 * NB;
   const size_t floats = rowowner_stream_floats(n_sub);
-  hipError_t e = hipMalloc(&m->ro_stream, sizeof(float) * floats);
+  hipError_t e = m->ro_stream.ensure((long long)floats);
   if (e != hipSuccess) return e;
   if ((e = hipMemset(m->ro_stream, 0, sizeof(float) * floats)) != hipSuccess) return e;
-  if ((e = hipMalloc(&m->d_ro_sub, sizeof(RoSubnet) * n_sub)) != hipSuccess) return e;
+  if ((e = m->d_ro_sub.ensure(n_sub)) != hipSuccess) return e;
   std::vector<RoSubnet> tab(n_sub);
   for (int sidx = 0; sidx < n_sub; ++sidx) {
     const int b = NB - 1 - sidx / 2, which = 1 + (sidx & 1);
@@ -158,7 +158,7 @@ static hipError_t build_rowowner_stream_hip(ikf_model* m, const std::vector<int>
   }
   if ((e = hipMemcpy(m->d_ro_sub, tab.data(), sizeof(RoSubnet) * n_sub, hipMemcpyHostToDevice)) != hipSuccess) return e;
   const std::vector<RoSubnet> fwd = rowowner_fwd_table(tab, NB, d.D, perm_fwd);
-  if ((e = hipMalloc(&m->d_ro_sub_fwd, sizeof(RoSubnet) * n_sub)) != hipSuccess) return e;
+  if ((e = m->d_ro_sub_fwd.ensure(n_sub)) != hipSuccess) return e;
   if ((e = hipMemcpy(m->d_ro_sub_fwd, fwd.data(), sizeof(RoSubnet) * n_sub, hipMemcpyHostToDevice)) != hipSuccess) return e;
   if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
   // the XCD-local hand-over of the cluster form (G = 4 / 8 / 16) needs workgroups b and b + 8 k of a grid on one XCD: asked of the device once
@@ -367,13 +367,13 @@ extern "C" ikf_status ikf_load_weights(ikf_model* m, const ikf_tensor* tensors, 
     for (int k = 0; k < D; ++k) perm_fwd[(size_t)b * D + perm_host[(size_t)b * D + k]] = k;
 
   // upload
-  if (m->arena) { (void)hipFree(m->arena); m->arena = nullptr; }
-  if (!m->d_perm_inv) IKF_HIP(hipMalloc(&m->d_perm_inv, sizeof(int) * (size_t)NB * D));
-  if (!m->d_Minv) IKF_HIP(hipMalloc(&m->d_Minv, sizeof(float) * D * D));
-  if (!m->d_M) IKF_HIP(hipMalloc(&m->d_M, sizeof(float) * D * D));
-  if (!m->d_perm) IKF_HIP(hipMalloc(&m->d_perm, sizeof(int) * (size_t)NB * D));
-  if (!m->d_blin) IKF_HIP(hipMalloc(&m->d_blin, sizeof(float) * D));
-  IKF_HIP(hipMalloc(&m->arena, sizeof(float) * total));
+  m->arena.release();  // (a reload always reallocates: released first, so that ensure's grow-only test cannot keep the old array)
+  IKF_HIP(m->d_perm_inv.ensure((long long)NB * D));
+  IKF_HIP(m->d_Minv.ensure(D * D));
+  IKF_HIP(m->d_M.ensure(D * D));
+  IKF_HIP(m->d_perm.ensure((long long)NB * D));
+  IKF_HIP(m->d_blin.ensure(D));
+  IKF_HIP(m->arena.ensure((long long)total));
   m->arena_floats = total;
   IKF_HIP(hipMemcpy(m->arena, host.data(), sizeof(float) * total, hipMemcpyHostToDevice));
   IKF_HIP(hipMemcpy(m->d_perm_inv, perm_host.data(), sizeof(int) * (size_t)NB * D, hipMemcpyHostToDevice));
@@ -397,8 +397,8 @@ extern "C" ikf_status ikf_load_weights(ikf_model* m, const ikf_tensor* tensors, 
   }
   m->subnets = subs;
   // the split-32 weight images of the f16-split contraction are built on the device when that mode is selected
-  if (m->split_arena) { (void)hipFree(m->split_arena); m->split_arena = nullptr; }
-  if (m->split_frag_arena) { (void)hipFree(m->split_frag_arena); m->split_frag_arena = nullptr; }
+  m->split_arena.release();
+  m->split_frag_arena.release();
   m->w_mid_split.assign((size_t)2 * NB * 3, nullptr);
   m->w_mid_split_frag.assign((size_t)2 * NB * 3, nullptr);
   // The f32 images first and unconditionally: whatever happens to the f16x3 images below, every batch size of the f32 path

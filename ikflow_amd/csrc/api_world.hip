@@ -50,7 +50,7 @@ extern "C" ikf_status ikf_set_world(ikf_model* m, const ikf_obstacle* h_obstacle
     }
   }
   IKF_ON_DEVICE(m)
-  if (!m->d_world) IKF_HIP(hipMalloc(&m->d_world, sizeof(WorldModel)));
+  IKF_HIP(m->d_world.ensure(1));
   IKF_HIP(hipMemcpy(m->d_world, &wm, sizeof(WorldModel), hipMemcpyHostToDevice));
   m->world_n = n_obstacles;
   m->world_min_clearance = min_clearance;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ikf_internal.h"
+#include "device_buf.h"  // DeviceBuf / PinnedBuf: every allocation of the handle is owned by a member of one of these types
 
 using namespace ikf;  // (this header is for the API units alone)
 
@@ -42,28 +43,6 @@ struct DeviceGuard {
   DeviceGuard dev_guard_((m)->device);                                                                         \
   if (dev_guard_.err != hipSuccess)                                                                            \
     return fail(IKF_ERR_HIP, std::string("hipSetDevice failed: ") + hipGetErrorString(dev_guard_.err));
-
-// A device array that only grows (the candidate stage's buffers).  ensure(n): nothing when it already holds n elements; otherwise the old
-// array is freed BEFORE the new one is allocated, and a failed hipMalloc leaves it empty - nothing leaked, no dangling pointer.  No destructor:
-// the handle's buffers are released by ikf_destroy, under its DeviceGuard.
-template <class T>
-struct DeviceBuf {
-  T* p = nullptr;
-  long long cap = 0;  // elements
-  hipError_t ensure(long long n) {
-    if (n <= cap) return hipSuccess;
-    release();
-    hipError_t e = hipMalloc(&p, sizeof(T) * (size_t)n);
-    if (e == hipSuccess) cap = n;
-    else p = nullptr;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
 
 struct ikf_model {
   int device = 0;
@@ -96,20 +75,20 @@ struct ikf_model {
   //   chain_mode: 0 off, 1 on (ikf_set_gemm_variant 170 / 171); chain_census: -1 not yet taken, 0 the dispatcher does not hand 32
   //   workgroups to each of 8 XCDs on this device (the chain is never used), 1 verified
   int chain_mode = 0, chain_census = -1;
-  ChainSubnet* d_chain_tab = nullptr;  // [2 nb_nodes] per-subnet arguments, rebuilt when the weights or the scratch change
+  DeviceBuf<ChainSubnet> d_chain_tab;  // [2 nb_nodes] per-subnet arguments, rebuilt when the weights or the scratch change
   bool chain_tab_valid = false;
-  unsigned* d_chain_ctl = nullptr;     // [IKF_CHAIN_CTL_WORDS], zero between calls (the launch's last workgroup re-zeroes it)
-  unsigned* d_arrive = nullptr;  // [kArriveWords] row-tile arrival counters of the fused tail (zeroed by every call's first entry kernel)
-  int* h_give_up = nullptr;      // pinned, device-visible: set by a workgroup whose in-launch wait ran out
+  DeviceBuf<unsigned> d_chain_ctl;     // [IKF_CHAIN_CTL_WORDS], zero between calls (the launch's last workgroup re-zeroes it)
+  DeviceBuf<unsigned> d_arrive;  // [kArriveWords] row-tile arrival counters of the fused tail (zeroed by every call's first entry kernel)
+  PinnedBuf<int> h_give_up;      // pinned, device-visible: set by a workgroup whose in-launch wait ran out
   int precision = 0;      // 0: hidden contractions on the exact-f32 MFMA; 1: error-compensated 3x f16 MFMA split
   int lm_precision = 1;   // LM step: 1 fp64 inside (Cholesky), 0 the reference's fp32 arithmetic (LU, partial pivoting) - ikf_set_lm_precision
-  uint16_t* split_arena = nullptr;  // split-32 images of the hidden Linear weights
+  DeviceBuf<uint16_t> split_arena;  // split-32 images of the hidden Linear weights
   std::vector<const void*> w_mid_split;  // [subnet][layer] -> device pointer (flattened: subnet*3 + layer)
-  float* split_frag_arena = nullptr;     // fragment-major copies of the split-32 images (small-batch f16-split kernel)
+  DeviceBuf<float> split_frag_arena;     // fragment-major copies of the split-32 images (small-batch f16-split kernel)
   std::vector<const void*> w_mid_split_frag;
   // fragment-major images of the hidden Linear weights (small-batch per-layer kernels, <= 512 rows): built by the first chunk that needs
   // them, or ahead of time by ikf_reserve - a handle whose small batches run the cluster form never pays the 201 MB / the pack launches
-  float* wfrag_arena = nullptr;
+  DeviceBuf<float> wfrag_arena;
   bool wfrag_built = false;
   double load_ms = 0.0, frag_ms = 0.0;   // host wall time of the last ikf_load_weights (device work included) / of building these images
   std::vector<const float*> w_mid_frag;  // [subnet][layer], same flattening; null when the width does not fit
@@ -118,8 +97,8 @@ struct ikf_model {
   // them from `ro_stream` (the subnets' parameters in execution and consumption order, +203 MB for Panda).  Taken for the full rounds of
   // n_cu x 16 rows of a batch and for a last partial round of at least ro_min_tail rows; the rest runs on the per-layer kernels.
   //   ro_mode: -1 by batch size, 0 never, 1 always (ikf_set_gemm_variant 180 / 181 / 182)
-  float* ro_stream = nullptr;
-  RoSubnet* d_ro_sub = nullptr;
+  DeviceBuf<float> ro_stream;
+  DeviceBuf<RoSubnet> d_ro_sub;
   int ro_mode = -1, ro_nbuf = 4;
   int n_cu = 256;
   long long ro_min_tail = -1;  // -1: the last partial round goes to whatever plan_tail finds cheapest; >= 0 (probes): to the row-owner launch from that many rows on
@@ -129,8 +108,8 @@ struct ikf_model {
   // handle stops using the form (cl_give_up).   cl_mode: -1 by batch size, 0 never, 1 whenever the grid fits (ikf_set_gemm_variant 185 / 186 / 187)
   int cl_mode = -1;
   long long cl_rows = 0;          // row capacity of the exchange buffers
-  float* cl_xbuf = nullptr;       // [tiles][16][1024]
-  float* cl_sync = nullptr;       // partial sums, epoch words, abort word (one memset per launch)
+  DeviceBuf<float> cl_xbuf;       // [tiles][16][1024]
+  DeviceBuf<float> cl_sync;       // partial sums, epoch words, abort word (one memset per launch)
   // The drain-free hand-over (r05, flow_rowowner.hip TAG): every exchanged float carries its subnet's parity in the last mantissa bit, so a
   // producer neither drains its stores nor publishes an epoch and a consumer validates what it reads.  Taken for G = 2 .. 16 (- 3 .. 4.5 %
   // per call, and no memset in front of the launch; with 32 members the early re-reads of whole slices cost more than the epoch words).
@@ -139,11 +118,11 @@ struct ikf_model {
   // the next one (until then every tagged launch returns at once and its repair launch does the work: the abort word stays set).
   //   cl_tagged: 1 (default) / 0 (ikf_set_gemm_variant 193 / 192)
   int cl_tagged = 1;
-  float* cl_xbuf_t = nullptr;
-  float* cl_sync_t = nullptr;
+  DeviceBuf<float> cl_xbuf_t;
+  DeviceBuf<float> cl_sync_t;
   size_t cl_sync_t_bytes = 0;
   bool cl_tag_dirty = false;
-  int* h_cl_give_up = nullptr;    // pinned, device-visible
+  PinnedBuf<int> h_cl_give_up;    // pinned, device-visible
   int cl_drop_next = 0;           // tests: the next cluster launch runs one workgroup short (ikf_set_gemm_variant 188): its tile's waits run out
   long long cl_repairs = 0;       // give-ups seen so far (ikf_cluster_repairs)
   // A wait that ran out means a peer was not resident - another process's kernel held CUs just then.  That tenant may be gone a second
@@ -163,39 +142,39 @@ struct ikf_model {
                                   // peer on another XCD (placement is verified in the launch, never assumed) or by ikf_set_gemm_variant 189
 
   // packed weights (one arena)
-  float* arena = nullptr;
+  DeviceBuf<float> arena;
   size_t arena_floats = 0;
   std::vector<SubnetWeights> subnets;  // [2*block + (which-1)]
-  int* d_perm_inv = nullptr;           // [nb_nodes][D]
-  float* d_Minv = nullptr;             // [D][D]
+  DeviceBuf<int> d_perm_inv;           // [nb_nodes][D]
+  DeviceBuf<float> d_Minv;             // [D][D]
   // forward (training-direction) pass, ikf_flow_forward
-  float* d_M = nullptr;                // [D][D] FixedLinearTransform forward matrix (module_list.0.M, or the fp64 inverse of M_inv)
-  int* d_perm = nullptr;               // [nb_nodes][D] PermuteRandom forward: perm[perm_inv[k]] = k
+  DeviceBuf<float> d_M;                // [D][D] FixedLinearTransform forward matrix (module_list.0.M, or the fp64 inverse of M_inv)
+  DeviceBuf<int> d_perm;               // [nb_nodes][D] PermuteRandom forward: perm[perm_inv[k]] = k
   float log_det_M = 0.f;               // logDetM = log|det M|, fp64 at load
   float log_det_Minv = 0.f;            // log|det M_inv| of the M_inv that is uploaded (ikf_flow_inverse), fp64 at load - not -log_det_M
-  RoSubnet* d_ro_sub_fwd = nullptr;    // the row-owner table in forward execution order (rowowner_fwd_table)
-  float* d_blin = nullptr;             // [D]
-  Chain* d_chain = nullptr;            // robot chain + limits
-  CollisionModel* d_collision = nullptr;  // capsules + pairs (ikf_set_collision_model), or null
+  DeviceBuf<RoSubnet> d_ro_sub_fwd;    // the row-owner table in forward execution order (rowowner_fwd_table)
+  DeviceBuf<float> d_blin;             // [D]
+  DeviceBuf<Chain> d_chain;            // robot chain + limits
+  DeviceBuf<CollisionModel> d_collision;  // capsules + pairs (ikf_set_collision_model), or null
 
   // scratch
   long long chunk_rows = 0;  // capacity of the per-chunk flow scratch
-  float* xbuf = nullptr;     // [chunk][D]
-  float* xbuf2 = nullptr;    // [chunk][D]   second state buffer (fused path ping-pongs the state)
-  float* pbuf = nullptr;     // [slots][chunk][IKF_PSTRIDE] last-Linear partial sums (fused path)
+  DeviceBuf<float> xbuf;     // [chunk][D]
+  DeviceBuf<float> xbuf2;    // [chunk][D]   second state buffer (fused path ping-pongs the state)
+  DeviceBuf<float> pbuf;     // [slots][chunk][IKF_PSTRIDE] last-Linear partial sums (fused path)
   float* pbuf_alt = nullptr; // second set for odd subnets when a subnet has ONE hidden contraction (see ensure_scratch); else == pbuf
-  float* hA = nullptr;       // [chunk][width]
-  float* hB = nullptr;
+  DeviceBuf<float> hA;       // [chunk][width]
+  DeviceBuf<float> hB;
   // exact-IK scratch
   long long exact_rows = 0, exact_poses = 0;
   long long exact_upfront_rows = 32LL << 20;  // ikf_set_exact_upfront_rows
-  float* ex_q = nullptr;          // [rows][ndof]
-  uint8_t* ex_row_valid = nullptr;  // [rows]
-  unsigned* ex_pose_first = nullptr;  // [poses] earliest valid iteration over a pose's repeats in the running round (early-exit hint)
-  int* ex_pose_idx = nullptr;     // [poses]
-  int* ex_block_scratch = nullptr;  // [2 * compact_blocks(poses)] per-block counts / offsets of the ordered compaction
-  int* ex_count = nullptr;        // device
-  int* h_count = nullptr;         // pinned host
+  DeviceBuf<float> ex_q;          // [rows][ndof]
+  DeviceBuf<uint8_t> ex_row_valid;  // [rows]
+  DeviceBuf<unsigned> ex_pose_first;  // [poses] earliest valid iteration over a pose's repeats in the running round (early-exit hint)
+  DeviceBuf<int> ex_pose_idx;     // [poses]
+  DeviceBuf<int> ex_block_scratch;  // [2 * compact_blocks(poses)] per-block counts / offsets of the ordered compaction
+  DeviceBuf<int> ex_count;        // device
+  PinnedBuf<int> h_count;         // pinned host
   // best-of-K ranking scratch (api_rank.hip): the flow's candidate rows and the K-chunks' partial lists
   int n_caps = 0;                 // capsules of d_collision (sizes the ranking kernel's LDS)
   DeviceBuf<float> rk_q;          // [rows][ndof]
@@ -209,12 +188,12 @@ struct ikf_model {
   // diverse-of-K scratch (api_diverse.hip; the candidate rows are rk_q, the partial lists the ranking's): the row scores
   DeviceBuf<float> dv_score;      // [rows]
   // world collision (api_world.hip): the caller's obstacles; with world_n > 0 the ranking kernel also rejects rows closer than world_min_clearance
-  WorldModel* d_world = nullptr;  // allocated by the first ikf_set_world with obstacles
+  DeviceBuf<WorldModel> d_world;  // allocated by the first ikf_set_world with obstacles
   int world_n = 0;
   float world_min_clearance = 0.f;
   // f16x3 range guard
-  int* d_split_flag = nullptr;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
-  int* h_split_flag = nullptr;    // pinned host
+  DeviceBuf<int> d_split_flag;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
+  PinnedBuf<int> h_split_flag;    // pinned host
   int split_guard = 1;
   long long split_fallbacks = 0;
 
