@@ -19,6 +19,7 @@ IKF_PATH_MAX_K = 256
 IKF_DIVERSE_MAX_K = 1024
 IKF_DIVERSE_MAX_KEEP = 16
 IKF_WORLD_MAX_OBSTACLES = 64
+IKF_SWEEP_MAX_SAMPLES = 16
 IKF_OBSTACLE_SPHERE, IKF_OBSTACLE_CAPSULE, IKF_OBSTACLE_HALF_SPACE, IKF_OBSTACLE_BOX = 0, 1, 2, 3
 
 IKF_OK = 0
@@ -242,6 +243,14 @@ WORLD_SIGNATURES = {
     "ikf_world_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# ... every symbol include/ikflow_amd_sweep.h declares (swept collision checks along edges: the caller's, and those of a path lattice)
+SWEEP_SIGNATURES = {
+    "ikf_set_path_sweep": (C.c_int, [C.c_void_p, C.c_int]),
+    "ikf_get_path_sweep": (C.c_int, [C.c_void_p]),
+    # q_a, q_b, n, n_samples, reject_self, self_min_clearance, blocked_out, first_out, stream
+    "ikf_sweep_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 LIB_PATH = _build.LIB_PATH
 _libs = {}
 
@@ -265,7 +274,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -9,6 +9,13 @@ static ikf_status ensure_path_scratch(ikf_model* m, long long rows) {
   IKF_HIP(m->pt_bp.ensure(path_bp_bytes(rows, 1)));
   return IKF_OK;
 }
+// the sweep's verdicts of a lattice of up to `rows` nodes of k candidates each (sweep_math.h): rows * ceil(k / 64) words
+static ikf_status ensure_path_mask(ikf_model* m, long long rows, int k) {
+  IKF_HIP(m->pt_edge_free.ensure(rows * sweep_words(k)));
+  return IKF_OK;
+}
+// A sweep is set (ikf_set_path_sweep) and there is something to test against: obstacles on the handle, or the call rejects self-collisions.
+static bool path_sweeps(const ikf_model* m, const ikf_path_options* opt) { return m->path_sweep > 0 && (m->world_n > 0 || opt->reject_collisions); }
 // the shared latent expanded to one row per candidate row
 static ikf_status ensure_path_latent(ikf_model* m, long long rows) {
   IKF_HIP(m->pt_latent.ensure(rows * m->dims.D));
@@ -43,6 +50,30 @@ static ikf_status run_path(ikf_model* m, const float* d_waypoints, int64_t T, in
   a.index_out = d_index_out;
   a.cost_out = d_cost_out;
   a.reachable_out = d_reachable_out;
+  if (path_sweeps(m, opt)) {   // the edges of the lattice, S samples each, between the node stage and the search; the mask was sized by the caller
+    SweepArgs w{};
+    w.ch = m->d_chain;
+    w.cm = m->d_collision;
+    w.world = m->d_world;
+    w.n_obs = m->world_n;
+    w.n_caps = m->n_caps;
+    w.world_min_clearance = m->world_min_clearance;
+    w.reject_self = opt->reject_collisions ? 1 : 0;
+    w.self_min_clearance = opt->min_clearance;
+    w.n_samples = m->path_sweep;
+    w.lattice = 1;
+    w.q = d_q;
+    w.q_start = d_q_start;
+    w.node = node;
+    w.T = (int)T;
+    w.k = k;
+    w.max_joint_step = opt->max_joint_step;
+    w.edge_free = m->pt_edge_free.p;
+    IKF_HIP(prof_mark(m, s));   // bracketed like the sequential stage (tools/sweep_timing.py)
+    IKF_HIP(launch_sweep_edges(m->dims.ndof, w, s));
+    IKF_HIP(prof_mark(m, s));
+    a.edge_free = m->pt_edge_free.p;
+  }
   IKF_HIP(prof_mark(m, s));   // between ikf_profile_begin / _end the sequential stage is bracketed (tools/path_timing.py); otherwise nothing is recorded
   IKF_HIP(launch_path_lattice(m->dims.ndof, a, s));
   IKF_HIP(prof_mark(m, s));
@@ -58,6 +89,7 @@ extern "C" ikf_status ikf_path_search(ikf_model* m, const float* d_waypoints, in
   if (st != IKF_OK || nothing) return st;
   IKF_ON_DEVICE(m)
   st = ensure_path_scratch(m, T * (long long)k);
+  if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, T * (long long)k, k);
   if (st != IKF_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   StreamScope scope(m, s);
@@ -81,6 +113,7 @@ extern "C" ikf_status ikf_generate_path(ikf_model* m, const float* d_waypoints, 
   st = ensure_rank_rows(m, rows);
   if (st == IKF_OK) st = ensure_path_scratch(m, rows);
   if (st == IKF_OK && shared_latent) st = ensure_path_latent(m, rows);
+  if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, rows, k);
   if (st != IKF_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   StreamScope scope(m, s);
@@ -105,5 +138,6 @@ extern "C" ikf_status ikf_reserve_path(ikf_model* m, int64_t max_waypoints, int 
   const long long rows = max_waypoints * (long long)max_k;
   st = ensure_path_scratch(m, rows);
   if (st == IKF_OK && m->loaded) st = ensure_path_latent(m, rows);
+  if (st == IKF_OK && m->path_sweep > 0) st = ensure_path_mask(m, rows, max_k);   // (a sweep set later sizes its mask at the first call)
   return st;
 }

@@ -10,6 +10,7 @@
 #include "path_math.h"
 #include "diverse_math.h"
 #include "world_math.h"
+#include "sweep_math.h"
 
 namespace ikf {
 
@@ -467,6 +468,7 @@ struct PathArgs {
   int* index_out;             // [T]
   float* cost_out;            // [1]
   int* reachable_out;         // [T], or null
+  const uint64_t* edge_free;  // [T][k][sweep_words(k)] the sweep's verdicts (sweep_math.h), or null: no sweep - the lattice kernel as it was
 };
 hipError_t launch_path_expand_latent(const float* latent, int k, long long T, int D, float* out, hipStream_t s);
 hipError_t launch_path_lattice(int ndof, const PathArgs& a, hipStream_t s);
@@ -492,5 +494,34 @@ hipError_t launch_diverse_select(int ndof, const DiverseArgs& a, hipStream_t s);
 hipError_t launch_world_clearance(const Chain* d_chain, const CollisionModel* d_cm, int n_caps, const WorldModel* d_world, int n_obs,
                                   float min_clearance, int ndof, const float* q, long long n, float* clearance, int* obstacle, int* capsule,
                                   uint8_t* colliding, hipStream_t s);
+
+// sweep_kernels.hip - swept collision checks along edges (include/ikflow_amd_sweep.h; the arithmetic: sweep_math.h).  ONE kernel, two edge
+// sources: the caller's pairs (lattice == 0: lane = edge i of qa -> qb) and the edges of a path lattice (lattice != 0: one wave per word of
+// edge_free).  world null or n_obs == 0: no world rule.
+struct SweepArgs {
+  const Chain* ch;
+  const CollisionModel* cm;
+  const WorldModel* world;
+  int n_obs, n_caps;
+  float world_min_clearance;
+  int reject_self;
+  float self_min_clearance;
+  int n_samples;              // 1 .. IKF_SWEEP_MAX_SAMPLES
+  int lattice;
+  // pair source
+  const float* qa;            // [n][ndof]
+  const float* qb;            // [n][ndof]
+  long long n;
+  uint8_t* blocked_out;       // [n], or null
+  int* first_out;             // [n], or null
+  // lattice source
+  const float* q;             // [k * T][ndof] tile-major candidates
+  const float* q_start;       // [ndof], or null
+  const float* node;          // [k * T] node costs
+  int T, k;
+  float max_joint_step;
+  uint64_t* edge_free;        // [T][k][sweep_words(k)]
+};
+hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s);
 
 }  // namespace ikf

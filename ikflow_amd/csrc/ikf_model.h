@@ -1,6 +1,6 @@
 // The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
 // reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
-// those units (and api_rank / api_path / api_diverse / api_world) only; the kernel-launch interface is ikf_internal.h.
+// those units (and api_rank / api_path / api_diverse / api_world / api_sweep) only; the kernel-launch interface is ikf_internal.h.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -185,6 +185,9 @@ struct ikf_model {
   DeviceBuf<float> pt_node;       // [rows]
   DeviceBuf<uint8_t> pt_bp;       // [rows] a byte per node (+ padding: path_bp_bytes)
   DeviceBuf<float> pt_latent;     // [latent rows][D]
+  // swept edges of path IK (api_sweep.hip, api_path.hip): samples per lattice edge (0: no sweep) and the sweep kernel's verdicts, a bit per edge
+  int path_sweep = 0;
+  DeviceBuf<uint64_t> pt_edge_free;  // [T][k][sweep_words(k)]
   // diverse-of-K scratch (api_diverse.hip; the candidate rows are rk_q, the partial lists the ranking's): the row scores
   DeviceBuf<float> dv_score;      // [rows]
   // world collision (api_world.hip): the caller's obstacles; with world_n > 0 the ranking kernel also rejects rows closer than world_min_clearance

@@ -15,6 +15,11 @@
 //   gathered by all threads.  No atomics, no second workgroup, nothing read by the host.
 // LDS of the lattice workgroup (static): rows 2 x STAGE x 256 x 32 B = 32 KiB (reused by the walk back: 64 x 256 B = 16 KiB), node costs 4 KiB,
 // accumulated costs 2 KiB, wave hand-over 2 KiB: 40.3 KiB of a CU's 160 KiB.
+// SWEEP (a sweep is set on the handle and there is something to test against, include/ikflow_amd_sweep.h): PathArgs::edge_free holds the verdicts
+//   of k_sweep_edges, a bit per edge.  A thread keeps the (k + 63) / 64 words of its destination for the waypoints of the running stage in
+//   registers; those of the next stage are loaded with the stage prefetch that is in flight anyway, not on the sequential chain (at most
+//   4 x 64 bit per thread and waypoint).  Bit j is tested before predecessor j is offered to path_relax, bit 0 of row 0 before path_start with
+//   a q_start.  SWEEP = false is the kernel as it was.
 #include "ikf_internal.h"
 
 namespace ikf {
@@ -62,7 +67,27 @@ __device__ __forceinline__ void path_stage_store(const PathArgs& a, int buf, int
   for (int w = 0; w < IKF_PATH_STAGE; ++w) node[(buf * IKF_PATH_STAGE + w) * IKF_PATH_BLOCK + threadIdx.x] = prn[w];
 }
 
-template <int NDOF>
+constexpr int kPathMaskWords = (IKF_PATH_MAX_K + IKF_SWEEP_LANES - 1) / IKF_SWEEP_LANES;
+// the mask words of destination r for waypoints t0 .. t0 + wn - 1 into registers
+__device__ __forceinline__ void path_mask_load(const PathArgs& a, long long t0, int wn, int r, bool live, int words,
+                                               unsigned long long (&m)[IKF_PATH_STAGE][kPathMaskWords]) {
+#pragma unroll
+  for (int w = 0; w < IKF_PATH_STAGE; ++w)
+#pragma unroll
+    for (int x = 0; x < kPathMaskWords; ++x) m[w][x] = (live && w < wn && x < words) ? a.edge_free[sweep_word_index(t0 + w, r, x, a.k)] : 0ULL;
+}
+// bit j of the words of waypoint w of the stage (selects, so that the words stay in registers)
+__device__ __forceinline__ bool path_mask_bit(const unsigned long long (&m)[IKF_PATH_STAGE][kPathMaskWords], int w, int j) {
+  unsigned long long word = 0ULL;
+  const int x = j / IKF_SWEEP_LANES;
+#pragma unroll
+  for (int ww = 0; ww < IKF_PATH_STAGE; ++ww)
+#pragma unroll
+    for (int xx = 0; xx < kPathMaskWords; ++xx) word = (ww == w && xx == x) ? m[ww][xx] : word;
+  return (word >> (j % IKF_SWEEP_LANES)) & 1ULL;
+}
+
+template <int NDOF, bool SWEEP>
 __global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs a) {
   __shared__ float4 s_rows[kPathRowVecs];                               // [2][STAGE][256] rows of 8 floats
   __shared__ float s_node[2 * IKF_PATH_STAGE * IKF_PATH_BLOCK];        // [2][STAGE][256]
@@ -90,8 +115,12 @@ __global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs 
 
   const long long nstage = path_stages(T);
   float pre[IKF_PATH_STAGE * NDOF], prn[IKF_PATH_STAGE];
+  unsigned long long mask[IKF_PATH_STAGE][kPathMaskWords], mask_next[IKF_PATH_STAGE][kPathMaskWords];   // SWEEP: this stage's words, the next one's
+  const int mwords = SWEEP ? sweep_words(k) : 0;
+  (void)mask; (void)mask_next; (void)mwords;
   {
     const int wn0 = T < IKF_PATH_STAGE ? (int)T : IKF_PATH_STAGE;
+    if constexpr (SWEEP) path_mask_load(a, 0, wn0, r, live, mwords, mask_next);
     path_stage_load<NDOF>(a, 0, wn0, pre, prn);
     path_stage_store<NDOF>(a, 0, wn0, pre, prn, rows, s_node);
   }
@@ -103,6 +132,13 @@ __global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs 
     const int wn = T - t0 < IKF_PATH_STAGE ? (int)(T - t0) : IKF_PATH_STAGE;
     const bool more = s + 1 < nstage;
     const int wn_next = !more ? 0 : (T - t0 - IKF_PATH_STAGE < IKF_PATH_STAGE ? (int)(T - t0 - IKF_PATH_STAGE) : IKF_PATH_STAGE);
+    if constexpr (SWEEP) {
+#pragma unroll
+      for (int w = 0; w < IKF_PATH_STAGE; ++w)
+#pragma unroll
+        for (int x = 0; x < kPathMaskWords; ++x) mask[w][x] = mask_next[w][x];
+      if (more) path_mask_load(a, t0 + IKF_PATH_STAGE, wn_next, r, live, mwords, mask_next);
+    }
     if (more) path_stage_load<NDOF>(a, t0 + IKF_PATH_STAGE, wn_next, pre, prn);   // in flight while this stage is relaxed
     for (int w = 0; w < wn; ++w) {
       const long long t = t0 + w;
@@ -114,12 +150,17 @@ __global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs 
       }
       PathBest best = path_none();
       if (t == 0) {
-        if (live && sl == 0) best = path_start<NDOF>(qs, a.q_start != nullptr, me, step);
+        bool start_ok = true;
+        if constexpr (SWEEP) start_ok = a.q_start == nullptr || path_mask_bit(mask, w, 0);
+        if (live && sl == 0 && start_ok) best = path_start<NDOF>(qs, a.q_start != nullptr, me, step);
       } else if (live) {
         const int pbuf = w > 0 ? cur : cur ^ 1, pw = w > 0 ? w - 1 : IKF_PATH_STAGE - 1;   // waypoint t - 1: in this stage, or the last of the one before
         const float4* const pr = s_rows + (pbuf * IKF_PATH_STAGE + pw) * IKF_PATH_BLOCK * 2;
         const float* const pc = s_cost + pb * IKF_PATH_BLOCK;
         for (int j = sl; j < k; j += S) {
+          if constexpr (SWEEP) {
+            if (!path_mask_bit(mask, w, j)) continue;
+          }
           const float4 lo = pr[2 * j], hi = pr[2 * j + 1];
           const float pj[IKF_PATH_ROW] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
           path_relax<NDOF>(best, pc[j], pj, j, me, step);
@@ -208,7 +249,11 @@ static bool path_args_ok(const PathArgs& a) {
 
 hipError_t launch_path_lattice(int ndof, const PathArgs& a, hipStream_t s) {
   if (!path_args_ok(a) || !a.bp || !a.path_out || !a.index_out || !a.cost_out) return hipErrorInvalidValue;
-  IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND>), dim3(1), dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
+  if (a.edge_free) {
+    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND, true>), dim3(1), dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
+    return hipErrorInvalidValue;
+  }
+  IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND, false>), dim3(1), dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
   return hipErrorInvalidValue;
 }
 

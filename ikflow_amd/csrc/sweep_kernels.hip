@@ -1,0 +1,107 @@
+// Swept collision checks along edges for gfx950 (include/ikflow_amd_sweep.h): S interpolated configurations of every edge against the handle's
+// obstacles and, when asked for, the robot against itself.  The arithmetic is sweep_math.h; this kernel only places it.
+//
+// k_sweep_edges is ONE kernel with two edge sources, and both sources reach sweep_edge through the same call: the same source inlined into two
+// kernels was seen to be contracted differently, and a sample within an ulp of a threshold must get the same verdict
+// from ikf_sweep_edges and from a path call.
+//   pair source     lane = edge i of the caller's rows qa[i] -> qb[i]; writes a byte flag and the first blocked sample.
+//   lattice source  one wave per (waypoint t, destination r, block of 64 predecessors); lane = predecessor j of waypoint t - 1, the destination
+//                   row is wave-uniform.  The verdicts of a wave leave as ONE 64-bit word, __ballot(free), stored by one lane into
+//                   edge_free[t][r][word] - no atomics, no two waves touch a word.  Row t = 0 carries the start edge in bit 0 (all ones
+//                   without q_start).  A lane does no samples and reports 0 when its predecessor's or its destination's node cost is +inf or
+//                   the step gate forbids its edge: the search never takes such an edge, so no result depends on the pruned bit.
+// The geometry of k_world_clearance: 64-thread workgroups, the lane's capsule end points in LDS (one slice per lane, stride (6 n_caps) | 1: odd,
+// so the lanes' slices start in different banks), the obstacle table staged once per workgroup and read as a broadcast.  A workgroup walks
+// waves blockIdx.x, blockIdx.x + gridDim.x, ...  Samples in ascending order; a lane stops at its first blocked sample.
+#include "ikf_internal.h"
+
+namespace ikf {
+
+constexpr size_t kSweepMaxLds = sizeof(float) * ((size_t)IKF_WORLD_TABLE_WORDS + IKF_SWEEP_LANES * (size_t)(IKF_MAX_CAPSULES * 6 + 1));
+static_assert(kSweepMaxLds == 4096 + 37120, "obstacle table + one wave's capsule slices");
+static_assert(kSweepMaxLds <= 48 * 1024 && kSweepMaxLds <= 160 * 1024, "a sweep workgroup fits the default dynamic LDS and a CU");
+constexpr long long kSweepMaxGrid = 1LL << 20;
+
+template <int NDOF>
+__global__ __launch_bounds__(IKF_SWEEP_LANES) void k_sweep_edges(const SweepArgs a) {
+  extern __shared__ float sweep_lds[];   // [n_obs x 16] obstacle table, then [64][cap_stride] capsule end points
+  const int lane = threadIdx.x;
+  const int n_obs = a.n_obs;
+  float* const OBS = sweep_lds;
+  const float* const src = n_obs > 0 ? reinterpret_cast<const float*>(a.world->obs) : nullptr;
+  for (int i = lane; i < n_obs * IKF_WORLD_OBSTACLE_WORDS; i += IKF_SWEEP_LANES) OBS[i] = src[i];
+  __syncthreads();
+  float* const w = sweep_lds + n_obs * IKF_WORLD_OBSTACLE_WORDS + lane * ((a.n_caps * 6) | 1);
+  const bool lattice = a.lattice != 0;
+  const long long T = a.T;
+  const int k = a.k;
+  const long long n_waves = lattice ? sweep_mask_words(T, k) : sweep_pair_waves(a.n);
+  for (long long wave = blockIdx.x; wave < n_waves; wave += gridDim.x) {
+    float ea[NDOF], eb[NDOF];
+#pragma unroll
+    for (int d = 0; d < NDOF; ++d) { ea[d] = 0.f; eb[d] = 0.f; }
+    bool active = false, all_free = false;
+    const long long i = wave * IKF_SWEEP_LANES + lane;   // pair source: the lane's edge
+    if (lattice) {
+      long long t;
+      int r, word;
+      sweep_wave_role(wave, k, &t, &r, &word);
+      const int j = word * IKF_SWEEP_LANES + lane;
+      const bool dest_ok = a.node[(long long)r * T + t] < rank_inf();
+      const float* pa = nullptr;
+      if (t == 0) {
+        all_free = a.q_start == nullptr;
+        if (a.q_start && j == 0 && dest_ok) pa = a.q_start;
+      } else if (j < k && dest_ok && a.node[(long long)j * T + t - 1] < rank_inf()) {
+        pa = a.q + ((long long)j * T + t - 1) * NDOF;
+      }
+      if (pa) {
+        const float* const pb = a.q + ((long long)r * T + t) * NDOF;
+        active = true;
+#pragma unroll
+        for (int d = 0; d < NDOF; ++d) {
+          ea[d] = pa[d];
+          eb[d] = pb[d];
+          const float df = eb[d] - ea[d];   // the step gate of path_edge
+          if (a.max_joint_step >= 0.f && fabsf(df) > a.max_joint_step) active = false;
+        }
+      }
+    } else if (i < a.n) {
+      active = true;
+      load_q<NDOF>(a.qa, i, ea);
+      load_q<NDOF>(a.qb, i, eb);
+    }
+    int first = -1;
+    if (active)
+      first = sweep_edge<NDOF>(a.ch, a.cm, reinterpret_cast<const WorldObstacle*>(OBS), n_obs, a.world_min_clearance, a.reject_self != 0,
+                               a.self_min_clearance, ea, eb, a.n_samples, w);
+    if (lattice) {
+      const unsigned long long verdicts = __ballot(active && first < 0);
+      if (lane == 0) a.edge_free[wave] = all_free ? ~0ULL : verdicts;
+    } else if (i < a.n) {
+      if (a.blocked_out) a.blocked_out[i] = first >= 0 ? 1 : 0;
+      if (a.first_out) a.first_out[i] = first;
+    }
+  }
+}
+
+hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s) {
+  if (!a.ch || !a.cm || a.n_caps < 0 || a.n_caps > IKF_MAX_CAPSULES || a.n_obs < 0 || a.n_obs > IKF_WORLD_MAX_OBSTACLES || (a.n_obs > 0 && !a.world) ||
+      a.n_samples < 1 || a.n_samples > IKF_SWEEP_MAX_SAMPLES)
+    return hipErrorInvalidValue;
+  long long waves;
+  if (a.lattice) {
+    if (a.T < 1 || a.k < 1 || a.k > IKF_PATH_MAX_K || (long long)a.k * a.T > 0x7fffffffLL || !a.q || !a.node || !a.edge_free) return hipErrorInvalidValue;
+    waves = sweep_mask_words(a.T, a.k);
+  } else {
+    if (a.n <= 0) return hipSuccess;
+    if (!a.qa || !a.qb || (!a.blocked_out && !a.first_out)) return hipErrorInvalidValue;
+    waves = sweep_pair_waves(a.n);
+  }
+  const size_t lds = sizeof(float) * ((size_t)a.n_obs * IKF_WORLD_OBSTACLE_WORDS + IKF_SWEEP_LANES * (size_t)((a.n_caps * 6) | 1));
+  const unsigned grid = (unsigned)(waves < kSweepMaxGrid ? waves : kSweepMaxGrid);
+  IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
+  return hipGetLastError();
+}
+
+}  // namespace ikf

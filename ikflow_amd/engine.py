@@ -391,6 +391,31 @@ class Engine:
                                                   col.data_ptr(), self._stream()))
         return dist, obstacle, capsule, col.to(torch.bool)
 
+    # -- swept collision checks along edges (include/ikflow_amd_sweep.h) ------------------------------------
+    def set_path_sweep(self, n_samples: int) -> None:
+        """Samples per lattice edge of path_search / generate_path (0: no sweep, the default; at most 16).  While a sweep is set, an edge
+        whose interpolated configurations come closer to the world than its min_clearance - or, with reject_collisions, to the robot itself than
+        the options' min_clearance - is forbidden like a step-gate violation.  Not while calls on this engine are in flight on another stream."""
+        self._ck(self.lib.ikf_set_path_sweep(self._h, int(n_samples)))
+
+    @property
+    def path_sweep(self) -> int:
+        return int(self.lib.ikf_get_path_sweep(self._h))
+
+    def sweep_edges(self, q_a: torch.Tensor, q_b: torch.Tensor, n_samples: int, reject_self: bool = False,
+                    min_clearance: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Edges q_a[i] -> q_b[i] ([n x ndof] each), n_samples interior samples per edge against the engine's world (and, reject_self, the robot
+        itself with min_clearance) -> (blocked [n] bool, first blocked sample [n] int32, -1 where the edge is free)."""
+        q_a, q_b = self._q(q_a), self._q(q_b)
+        assert q_a.shape == q_b.shape, f"q_a and q_b must have the same shape, got {tuple(q_a.shape)} and {tuple(q_b.shape)}"
+        n = q_a.shape[0]
+        blocked = torch.empty(n, dtype=torch.uint8, device=self.device)
+        first = torch.empty(n, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_sweep_edges(self._h, q_a.data_ptr(), q_b.data_ptr(), n, int(n_samples), 1 if reject_self else 0,
+                                              float(min_clearance), blocked.data_ptr(), first.data_ptr(), self._stream()))
+        return blocked.to(torch.bool), first
+
     # -- best-of-K ranking (include/ikflow_amd_rank.h) -----------------------------------------------------
     @property
     def has_collision_model(self) -> bool:

@@ -130,6 +130,7 @@ class IKFlowSolver:
         self._model_weights_loaded = False
         self._engine = None  # created on first use, on the device of the inputs
         self._world = None   # (World, min_clearance) of set_world: re-applied to every engine this solver creates
+        self._path_sweep = 0  # samples per lattice edge of set_path_sweep: likewise
         # tests / tools only: "probes" binds lib/libikflow_amd_probes.so (the product + the priced-and-rejected forms of rounds 2 - 3);
         # set before the first call
         self.library_flavour = ""
@@ -178,6 +179,8 @@ class IKFlowSolver:
                     raise
             if self._world is not None:
                 self._push_world(eng)
+            if self._path_sweep:
+                eng.set_path_sweep(self._path_sweep)
             self._engine = eng
         return self._engine
 
@@ -208,6 +211,33 @@ class IKFlowSolver:
             eng.set_collision_model(*self._robot._collision_model)   # the solver's own handle, not the one Robot.config_self_collides uses
             eng._collision_source = self._robot._collision_model
         eng.set_world(*self._world)
+
+    def set_path_sweep(self, n_samples: int):
+        """Samples per edge of generate_ik_path's lattice (0: no sweep, the default; at most 16).  While set, the path also avoids every edge
+        whose n_samples interpolated configurations - q_i = a + i / (n_samples + 1) * (b - a) - come closer to the world of set_world than its
+        min_clearance or, with reject_self_collisions, to the robot itself than min_clearance (include/ikflow_amd_sweep.h).  Sampled, not
+        conservative: cover the gap between two samples with min_clearance."""
+        assert isinstance(n_samples, int) and not isinstance(n_samples, bool) and 0 <= n_samples <= 16, f"n_samples must be an int in 0 .. 16, got {n_samples!r}"
+        self._path_sweep = n_samples
+        if self._engine is not None:
+            self._engine.set_path_sweep(n_samples)
+
+    def path_collides(self, path: torch.Tensor, n_samples: int, reject_self: bool = False, min_clearance: float = 0.0) -> torch.Tensor:
+        """The swept check of a joint-space path [T x ndof]: per edge path[t] -> path[t + 1], whether one of its n_samples interpolated
+        configurations is closer to the world of set_world than its min_clearance or - reject_self - to the robot itself than min_clearance.
+        -> [T - 1] bool.  The rows themselves are not tested (Robot.config_collides_with_env does that)."""
+        assert isinstance(path, torch.Tensor) and path.ndim == 2 and path.shape[1] == self.ndof, f"path must be [T x {self.ndof}]"
+        assert isinstance(n_samples, int) and 1 <= n_samples <= 16, f"n_samples must be an int in 1 .. 16, got {n_samples!r}"
+        assert self._robot.has_collision_model, "path_collides needs a collision model (Robot.set_collision_capsules)"
+        with torch.inference_mode():
+            eng = self.engine(path.device)
+            if getattr(eng, "_collision_source", None) is not self._robot._collision_model:
+                eng.set_collision_model(*self._robot._collision_model)
+                eng._collision_source = self._robot._collision_model
+            if path.shape[0] < 2:
+                return torch.zeros(0, dtype=torch.bool, device=path.device)
+            rows = path.to(torch.float32).contiguous()
+            return eng.sweep_edges(rows[:-1].contiguous(), rows[1:].contiguous(), n_samples, reject_self, min_clearance)[0]
 
     def set_precision(self, mode: str):
         """Arithmetic of the hidden Linear contractions: "f32" (exact f32 MFMA, default) or "f16x3" (error-compensated
@@ -502,7 +532,7 @@ class IKFlowSolver:
         uses latent r at EVERY waypoint (the reference's visualizations.py oscillate_target(fixed_latent=True): under trained weights a fixed
         latent gives a solution that varies smoothly with the pose); otherwise as ``(k * T, dim)``, tile-major (row r * T + t is candidate r
         of waypoint t).  A candidate's node cost is ``pos_err + rot_weight * rot_err`` (metres), +inf when it is inadmissible (thresholds,
-        joint limits, self-collision and a world set by set_world as in generate_ranked_ik_solutions; nodes only, no swept test); the edge between consecutive candidates is their Euclidean joint
+        joint limits, self-collision and a world set by set_world as in generate_ranked_ik_solutions; edges are swept only under set_path_sweep); the edge between consecutive candidates is their Euclidean joint
         distance (no angle wrapping), forbidden when a joint moves by more than max_joint_step.  The path minimises
         ``sum of edges + node_weight * sum of node costs`` (+ the edge from q_start to the first configuration when q_start is given); ties
         go to the lower candidate index.

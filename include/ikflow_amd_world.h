@@ -22,7 +22,7 @@
  * While a world of n > 0 obstacles is set, a candidate row of ikf_rank_candidates, ikf_generate_ranked, ikf_path_search, ikf_generate_path,
  * ikf_diverse_select and ikf_generate_diverse is ALSO inadmissible (scores +inf exactly) when its world clearance is < the world's
  * min_clearance - whatever reject_collisions says: that flag and the options' own min_clearance keep meaning the robot against itself.
- * Path IK tests nodes only (no swept test along an edge).
+ * Path IK tests its nodes; the configurations along its edges only while a sweep is set (include/ikflow_amd_sweep.h).
  */
 #ifndef IKFLOW_AMD_WORLD_H
 #define IKFLOW_AMD_WORLD_H

@@ -1,0 +1,134 @@
+"""The arithmetic of swept collision checks (ikflow_amd/csrc/sweep_math.h: the sample configurations, the verdict of an edge, the geometry of the
+lattice's mask) compiled for the HOST with g++ and held against sequential numpy float32 and the fp64 reference of tests/sweep_helpers.py - the
+kernel's own source, checked without a GPU.  The GPU tests check the same code where it ships (tests/test_sweep.py).  Also here, from the fp64
+reference alone: every (chain, scene, S) the GPU tests use has few edges the reference cannot decide and enough on either side.
+Test infrastructure: nothing in ikflow_amd/ loads it."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import sweep_helpers as SH
+from test_kin_math_host import _chain_bytes
+from test_world_math_host import _set_capsules, _structs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def host_lib(tmp_path_factory):
+    out = tmp_path_factory.mktemp("sweep_math") / "libsweep_math_host.so"
+    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas", os.path.join(ROOT, "tests", "sweep_math_host.cpp"), "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lib = C.CDLL(str(out))
+    lib.kin_math_chain_bytes = lib.sweep_host_chain_bytes       # (what _chain_bytes asks the library it packs for)
+    lib.world_host_set_capsules = lib.sweep_host_set_capsules   # (what _set_capsules calls)
+    lib.sweep_host_set_capsules.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.sweep_host_set_capsules.restype = None
+    lib.sweep_host_set_world.argtypes = [C.c_void_p, C.c_int]
+    lib.sweep_host_samples.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]
+    lib.sweep_host_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p]
+    lib.sweep_host_mask_words.argtypes = [C.c_longlong, C.c_int]
+    lib.sweep_host_mask_words.restype = C.c_longlong
+    lib.sweep_host_word_index.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int]
+    lib.sweep_host_word_index.restype = C.c_longlong
+    lib.sweep_host_wave_role.argtypes = [C.c_longlong, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.sweep_host_wave_role.restype = None
+    lib.sweep_host_live_lanes.argtypes = [C.c_int, C.c_int]
+    lib.sweep_host_live_lanes.restype = C.c_ulonglong
+    lib.sweep_host_bit.argtypes = [C.c_void_p, C.c_int]
+    lib.sweep_host_pair_waves.argtypes = [C.c_longlong]
+    lib.sweep_host_pair_waves.restype = C.c_longlong
+    assert lib.sweep_host_max_samples() == SH.MAX_SAMPLES == 16
+    return lib
+
+
+@pytest.mark.parametrize("which", SH.CHAINS)
+def test_sample_configurations_equal_sequential_numpy_float32_bit_for_bit(host_lib, which):
+    """(a) S in {1, 3, 16}, ndof 5, 7 and 8 (a prismatic joint among them): q_i = a + f32(i) / f32(S + 1) * (b - a), every operation rounded on its own."""
+    a, b = SH.edges(which)
+    nd = a.shape[1]
+    assert nd == {"panda": 7, "fetch": 8, "syn5p": 5}[which]
+    for S in (1, 3, 16):
+        out = np.full((a.shape[0], S, nd), np.nan, np.float32)
+        assert host_lib.sweep_host_samples(nd, a.ctypes.data, b.ctypes.data, a.shape[0], S, out.ctypes.data) == 0
+        assert H.same_bits(out, SH.samples_f32(a, b, S)), (which, S)
+    # rows far apart and of mixed sign: the product f * d does round
+    rng = np.random.default_rng(5)
+    a2 = rng.uniform(-3, 3, (64, nd)).astype(np.float32)
+    b2 = rng.uniform(-3, 3, (64, nd)).astype(np.float32)
+    out = np.zeros((64, 16, nd), np.float32)
+    assert host_lib.sweep_host_samples(nd, a2.ctypes.data, b2.ctypes.data, 64, 16, out.ctypes.data) == 0
+    assert H.same_bits(out, SH.samples_f32(a2, b2, 16))
+
+
+def _first(lib, chain, c, rule):
+    n = c["a"].shape[0]
+    first = np.full(n, -7, np.int32)
+    assert lib.sweep_host_edges(chain, c["a"].ctypes.data, c["b"].ctypes.data, n, c["samples"].shape[1], int(rule in ("world", "both")), c["world_thr"],
+                                int(rule in ("self", "both")), c["self_thr"], first.ctypes.data) == 0
+    return first
+
+
+@pytest.mark.parametrize("which", SH.CHAINS)
+def test_verdicts_against_the_fp64_reference_and_the_condition_the_gpu_tests_rest_on(host_lib, which):
+    """(b) the kernel source's verdict and first blocked sample of every edge, under the world rule, the self rule and both: exact outside the band.
+    (c) from the reference alone, for every (scene, S) of the GPU tests: at most 5 % of the edges are in the band; under the world rule (threshold:
+    the median over the edges of their samples' least clearance) and under the self rule (threshold: the median over the samples, as
+    rank_helpers.clearance_threshold defines it) at least 20 % are surely blocked and at least 20 % surely free.  Under both rules at once an edge
+    is free only when both leave it free - about a quarter of the edges when the two are independent - so 20 % blocked and 10 % free are asked."""
+    robot, _ = H.kin_robots(which)
+    chain = _chain_bytes(robot, host_lib)
+    _set_capsules(host_lib, robot)
+    for scene, S in SH.EDGE_CASES:
+        c = SH.edge_case(which, scene, S)
+        assert host_lib.sweep_host_set_world(_structs(c["world"].obstacles), len(c["world"])) == 0
+        for rule in ("world", "self", "both"):
+            v = SH.case_verdicts(c, rule)
+            first = _first(host_lib, chain, c, rule)
+            assert ((first >= -1) & (first < S)).all()
+            SH.check_edges(first >= 0, first, v, f"{which} {scene} S {S} {rule}")
+            band, blocked, free = SH.shares(v)
+            print(f"{which} {scene} S {S} {rule}: band {band:.3f} blocked {blocked:.3f} free {free:.3f} of {len(first)} edges, "
+                  f"thresholds world {c['world_thr']:.4f} self {c['self_thr']:.4f}")
+            assert band <= 0.05, (which, scene, S, rule, band)
+            assert blocked >= 0.20 and free >= (0.10 if rule == "both" else 0.20), (which, scene, S, rule, blocked, free)
+    # nothing to test against: every edge is free
+    c = SH.edge_case(which, "mixed7", 3)
+    n = c["a"].shape[0]
+    first = np.full(n, -7, np.int32)
+    assert host_lib.sweep_host_edges(chain, c["a"].ctypes.data, c["b"].ctypes.data, n, 3, 0, 0.0, 0, 0.0, first.ctypes.data) == 0
+    assert (first == -1).all()
+
+
+def test_mask_geometry(host_lib):
+    """(d) k = 1, 63, 64, 65 and 256: words per destination, the word of an edge, the wave that produces it, the lanes that stand for a predecessor."""
+    for k in (1, 63, 64, 65, 256):
+        words = host_lib.sweep_host_words(k)
+        assert words == -(-k // 64)
+        for T in (1, 2, 7):
+            assert host_lib.sweep_host_mask_words(T, k) == T * k * words
+            seen = set()
+            for t in range(T):
+                for r in sorted({0, 1 % k, k // 2, k - 1}):
+                    for w in range(words):
+                        idx = host_lib.sweep_host_word_index(t, r, w, k)
+                        assert idx == (t * k + r) * words + w and idx not in seen and 0 <= idx < T * k * words
+                        seen.add(idx)
+                        tt, rr, ww = C.c_longlong(-1), C.c_int(-1), C.c_int(-1)
+                        host_lib.sweep_host_wave_role(idx, k, C.byref(tt), C.byref(rr), C.byref(ww))
+                        assert (tt.value, rr.value, ww.value) == (t, r, w)
+        live = [host_lib.sweep_host_live_lanes(k, w) for w in range(words + 1)]
+        assert live[words] == 0 and sum(bin(x).count("1") for x in live) == k
+        assert all(x == 2 ** 64 - 1 for x in live[:words - 1]) and live[words - 1] == 2 ** (k - 64 * (words - 1)) - 1
+        rng = np.random.default_rng(k)
+        bits = rng.integers(0, 2, k).astype(bool)
+        packed = np.zeros(words, np.uint64)
+        for j in np.flatnonzero(bits):
+            packed[j // 64] |= np.uint64(1) << np.uint64(j % 64)
+        assert [host_lib.sweep_host_bit(packed.ctypes.data, j) for j in range(k)] == [int(x) for x in bits]
+    assert [host_lib.sweep_host_pair_waves(n) for n in (0, 1, 63, 64, 65, 257)] == [0, 1, 1, 1, 2, 5]
