@@ -20,6 +20,7 @@ IKF_DIVERSE_MAX_K = 1024
 IKF_DIVERSE_MAX_KEEP = 16
 IKF_WORLD_MAX_OBSTACLES = 64
 IKF_SWEEP_MAX_SAMPLES = 16
+IKF_REFINE_MAX_STEPS = 16
 IKF_OBSTACLE_SPHERE, IKF_OBSTACLE_CAPSULE, IKF_OBSTACLE_HALF_SPACE, IKF_OBSTACLE_BOX = 0, 1, 2, 3
 
 IKF_OK = 0
@@ -251,6 +252,17 @@ SWEEP_SIGNATURES = {
     "ikf_sweep_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# ... every symbol include/ikflow_amd_refine.h declares (refined candidates: LM steps on every candidate row before it is scored)
+REFINE_SIGNATURES = {
+    "ikf_set_candidate_refine": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "ikf_get_candidate_refine": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    # target_poses, n_poses, k, q, n_steps, pos_tol, rot_tol, q_out, steps_out, converged_out, stream
+    "ikf_refine_candidates": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+}
+
 LIB_PATH = _build.LIB_PATH
 _libs = {}
 
@@ -274,7 +286,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -46,7 +46,12 @@ static ikf_status rank_check(ikf_model* m, const char* who, int64_t n, int k, co
 
 ikf_status ikf::flow_candidates(ikf_model* m, const float* d_poses, int64_t n, int k, const float* d_latent, int clamp_to_limits, hipStream_t s) {
   const PoseSource ps{d_poses, nullptr, (long long)n, 7, 0.0f};   // the tiling pose source of the exact path, without an index list
-  return run_flow_guarded(m, ps, d_latent, n * (long long)k, clamp_to_limits ? 1 : 0, m->rk_q.p, s);
+  ikf_status st = run_flow_guarded(m, ps, d_latent, n * (long long)k, clamp_to_limits ? 1 : 0, m->rk_q.p, s);
+  if (st != IKF_OK || m->refine_steps == 0) return st;
+  // refined candidates (include/ikflow_amd_refine.h): the one hook of ranked, diverse and path IK, in place on the rows the flow has just written
+  IKF_HIP(launch_refine(m->d_chain, m->dims.ndof, d_poses, n, k, m->rk_q.p, m->rk_q.p, m->refine_steps, m->refine_pos_tol, m->refine_rot_tol, nullptr,
+                        nullptr, m->lm_precision, s));
+  return IKF_OK;
 }
 
 ikf_status ikf::score_candidates(ikf_model* m, const float* d_poses, int64_t n, int k, const float* d_q, const float* d_q_ref,

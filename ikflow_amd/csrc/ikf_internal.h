@@ -11,6 +11,7 @@
 #include "diverse_math.h"
 #include "world_math.h"
 #include "sweep_math.h"
+#include "refine_math.h"
 
 namespace ikf {
 
@@ -523,5 +524,10 @@ struct SweepArgs {
   uint64_t* edge_free;        // [T][k][sweep_words(k)]
 };
 hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s);
+
+// refine_kernels.hip - refined candidates (include/ikflow_amd_refine.h; the arithmetic: refine_math.h).  q [k * n_poses][ndof] tile-major, the
+// pose of row r is r % n_poses; q_out may be q_in; steps_out / converged_out [k * n_poses], each nullable.  lm_precision as launch_lm_step.
+hipError_t launch_refine(const Chain* d_chain, int ndof, const float* poses, long long n_poses, int k, const float* q_in, float* q_out, int n_steps,
+                         float pos_tol, float rot_tol, uint8_t* steps_out, uint8_t* converged_out, int lm_precision, hipStream_t s);
 
 }  // namespace ikf

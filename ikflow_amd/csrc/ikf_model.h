@@ -1,6 +1,6 @@
 // The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
 // reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
-// those units (and api_rank / api_path / api_diverse / api_world / api_sweep) only; the kernel-launch interface is ikf_internal.h.
+// those units (and api_rank / api_path / api_diverse / api_world / api_sweep / api_refine) only; the kernel-launch interface is ikf_internal.h.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -188,6 +188,9 @@ struct ikf_model {
   // swept edges of path IK (api_sweep.hip, api_path.hip): samples per lattice edge (0: no sweep) and the sweep kernel's verdicts, a bit per edge
   int path_sweep = 0;
   DeviceBuf<uint64_t> pt_edge_free;  // [T][k][sweep_words(k)]
+  // refined candidates (api_refine.hip, api_rank.hip): LM steps on the flow's candidate rows before they are scored (0: none) and their tolerances
+  int refine_steps = 0;
+  float refine_pos_tol = 0.f, refine_rot_tol = 0.f;
   // diverse-of-K scratch (api_diverse.hip; the candidate rows are rk_q, the partial lists the ranking's): the row scores
   DeviceBuf<float> dv_score;      // [rows]
   // world collision (api_world.hip): the caller's obstacles; with world_n > 0 the ranking kernel also rejects rows closer than world_min_clearance
@@ -288,7 +291,8 @@ ikf_status ensure_rank_rows(ikf_model* m, long long rows);   // the candidate ro
 // collision model, then the empty call (*nothing_to_do) and, last, null device pointers (`have_pointers`: the family's required ones).
 ikf_status check_candidates(const ikf_model* m, const std::string& who, const char* count, int64_t n, int k, int k_max, const void* opt,
                             bool reject_collisions, const char* rule_fault, bool have_pointers, bool* nothing_to_do);
-// The flow on k tiled candidates per pose (latent [k * n][D]; the conditional of row r * n + j is pose j) into rk_q, which the caller has sized.
+// The flow on k tiled candidates per pose (latent [k * n][D]; the conditional of row r * n + j is pose j) into rk_q, which the caller has sized -
+// and, while a refinement is set on the handle (ikf_set_candidate_refine), its LM steps on those rows, in place: whatever follows sees refined rows.
 ikf_status flow_candidates(ikf_model* m, const float* d_poses, int64_t n, int k, const float* d_latent, int clamp_to_limits, hipStream_t s);
 // The one place that fills a RankArgs and launches the ranking kernel: chunking, capsule slices, the handle's world, the partial lists.
 ikf_status score_candidates(ikf_model* m, const float* d_poses, int64_t n, int k, const float* d_q, const float* d_q_ref,

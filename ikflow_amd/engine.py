@@ -416,6 +416,39 @@ class Engine:
                                               float(min_clearance), blocked.data_ptr(), first.data_ptr(), self._stream()))
         return blocked.to(torch.bool), first
 
+    # -- refined candidates (include/ikflow_amd_refine.h) ------------------------------------------------------
+    def set_candidate_refine(self, n_steps: int, pos_tol: float = 0.0, rot_tol: float = 0.0) -> None:
+        """LM steps on every candidate row of generate_ranked / generate_diverse / generate_path, between the flow and the scoring (0: none, the
+        default; at most 16).  A row stops after the first step that leaves it below both tolerances (metres, radians; 0: never - all steps run).
+        While set, scores, thresholds, limit / collision / world rejection, distances, lattice edges, the sweep and the returned rows are those
+        of the refined rows.  Not while calls on this engine are in flight on another stream."""
+        self._ck(self.lib.ikf_set_candidate_refine(self._h, int(n_steps), float(pos_tol), float(rot_tol)))
+
+    def candidate_refine(self) -> Tuple[int, float, float]:
+        """-> (n_steps, pos_tol, rot_tol) in force on this engine; n_steps 0: no refinement."""
+        pos, rot = C.c_float(0.0), C.c_float(0.0)
+        n = int(self.lib.ikf_get_candidate_refine(self._h, C.byref(pos), C.byref(rot)))
+        return n, float(pos.value), float(rot.value)
+
+    def refine_candidates(self, target_poses: torch.Tensor, k: int, q: torch.Tensor, n_steps: int, pos_tol: float = 0.0, rot_tol: float = 0.0,
+                          return_info: bool = False):
+        """target_poses [m x 7]; q [k * m x ndof] tile-major (row r * m + j = candidate r of pose j): up to n_steps LM steps on every row, each
+        stopping after the first step that leaves it below both tolerances -> q [k * m x ndof], or (q, steps [k * m] uint8, converged [k * m] bool)
+        with return_info.  The caller's own rows: the engine's set_candidate_refine state plays no part."""
+        tp = self._on_device(target_poses, "target_poses")
+        assert tp.ndim == 2 and tp.shape[1] == 7, f"target_poses must be of shape [m x 7], got {tuple(tp.shape)}"
+        m = tp.shape[0]
+        q = self._q(q)
+        assert q.shape[0] == k * m, f"q must be [{k * m} x {self.layout.ndof}] (tile-major), got {tuple(q.shape)}"
+        out = torch.empty_like(q)
+        steps = torch.empty(k * m, dtype=torch.uint8, device=self.device) if return_info else None
+        conv = torch.empty(k * m, dtype=torch.uint8, device=self.device) if return_info else None
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_refine_candidates(
+                self._h, tp.data_ptr(), m, int(k), q.data_ptr(), int(n_steps), float(pos_tol), float(rot_tol), out.data_ptr(),
+                None if steps is None else steps.data_ptr(), None if conv is None else conv.data_ptr(), self._stream()))
+        return (out, steps, conv.to(torch.bool)) if return_info else out
+
     # -- best-of-K ranking (include/ikflow_amd_rank.h) -----------------------------------------------------
     @property
     def has_collision_model(self) -> bool:

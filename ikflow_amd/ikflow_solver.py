@@ -131,6 +131,7 @@ class IKFlowSolver:
         self._engine = None  # created on first use, on the device of the inputs
         self._world = None   # (World, min_clearance) of set_world: re-applied to every engine this solver creates
         self._path_sweep = 0  # samples per lattice edge of set_path_sweep: likewise
+        self._candidate_refine = (0, 0.0, 0.0)  # (n_steps, pos_tol, rot_tol) of set_candidate_refine: likewise
         # tests / tools only: "probes" binds lib/libikflow_amd_probes.so (the product + the priced-and-rejected forms of rounds 2 - 3);
         # set before the first call
         self.library_flavour = ""
@@ -181,6 +182,8 @@ class IKFlowSolver:
                 self._push_world(eng)
             if self._path_sweep:
                 eng.set_path_sweep(self._path_sweep)
+            if self._candidate_refine[0]:
+                eng.set_candidate_refine(*self._candidate_refine)
             self._engine = eng
         return self._engine
 
@@ -221,6 +224,20 @@ class IKFlowSolver:
         self._path_sweep = n_samples
         if self._engine is not None:
             self._engine.set_path_sweep(n_samples)
+
+    def set_candidate_refine(self, n_steps: int, pos_tol: float = mm_to_m(1), rot_tol: float = 0.1):
+        """Levenberg-Marquardt steps on EVERY candidate of generate_ranked_ik_solutions, generate_diverse_ik_solutions and generate_ik_path,
+        between the flow and the scoring (0: none, the default; at most 16).  A candidate stops after the first step that leaves its pose error
+        below both tolerances (the defaults are generate_exact_ik_solutions' thresholds; 0: never, all steps run; a rot_tol at or below 9.77e-4
+        rad never stops one).  While set, every threshold, joint-limit, self-collision, world and swept-edge test, every score and distance and
+        every returned row is that of the refined candidate (include/ikflow_amd_refine.h)."""
+        assert isinstance(n_steps, int) and not isinstance(n_steps, bool) and 0 <= n_steps <= 16, f"n_steps must be an int in 0 .. 16, got {n_steps!r}"
+        for name, tol in (("pos_tol", pos_tol), ("rot_tol", rot_tol)):
+            assert isinstance(tol, (int, float)) and not isinstance(tol, bool) and math.isfinite(tol) and tol >= 0, (
+                f"{name} must be a finite number >= 0, got {tol!r}")
+        self._candidate_refine = (n_steps, float(pos_tol), float(rot_tol)) if n_steps else (0, 0.0, 0.0)
+        if self._engine is not None:
+            self._engine.set_candidate_refine(*self._candidate_refine)
 
     def path_collides(self, path: torch.Tensor, n_samples: int, reject_self: bool = False, min_clearance: float = 0.0) -> torch.Tensor:
         """The swept check of a joint-space path [T x ndof]: per edge path[t] -> path[t + 1], whether one of its n_samples interpolated
@@ -429,7 +446,8 @@ class IKFlowSolver:
         generate_exact_ik_solutions' default thresholds, 1 mm / 0.1 rad).  Inadmissible: an error not below its threshold (when given), a
         joint strictly outside its limits (reject_joint_limits), a clearance below min_clearance (reject_self_collisions; None = when the
         robot carries a capsule model).  A world set by set_world is in force: a candidate closer to an obstacle than the world's
-        min_clearance is inadmissible too.  Candidates are ordered by (score, sample index).
+        min_clearance is inadmissible too.  Candidates are ordered by (score, sample index).  Under set_candidate_refine every candidate is
+        LM-refined first, and all of the above is that of the refined candidate.
 
         Returns the named tuple (solutions [m x n_keep x ndof], scores [m x n_keep], repeat_index [m x n_keep] int32, n_admissible [m]
         int32[, row_scores [k * m]]); slots beyond a pose's admissible candidates hold 0 / +inf / -1."""
@@ -475,7 +493,8 @@ class IKFlowSolver:
         selection on the GPU without a host round trip (include/ikflow_amd_diverse.h).
 
         y: [7] or [m x 7]; 1 <= k <= 1024, 1 <= n_keep <= min(k, 16).  Latent layout, scores and admissibility are those of
-        generate_ranked_ik_solutions (without a reference configuration; a world set by set_world is in force).  Slot 0 is that method's first choice; every later slot is the
+        generate_ranked_ik_solutions (without a reference configuration; a world set by set_world is in force; under set_candidate_refine the
+        candidates are LM-refined first, and scores, admissibility and distances are those of the refined candidates).  Slot 0 is that method's first choice; every later slot is the
         admissible sample farthest (Euclidean in joint space, no angle wrapping; joint j scaled by a finite joint_weights[j] >= 0 when given) from
         the ones kept so far, ties to the lower sample index.  A pose's selection stops when no sample is left or the farthest one is
         closer than min_separation to a kept one: kept rows are pairwise at least min_separation apart, and when fewer than n_keep are
@@ -538,7 +557,9 @@ class IKFlowSolver:
         go to the lower candidate index.
 
         refine_steps > 0 applies that many Levenberg-Marquardt steps to the T chosen rows when a path exists; ``index`` and ``cost`` (and
-        ``n_reachable``, ``node_costs``) still describe the unrefined lattice.
+        ``n_reachable``, ``node_costs``) still describe the unrefined lattice.  set_candidate_refine is the other order: it refines all k * T
+        candidates BEFORE the lattice is built, so node costs, admissibility, edges, the step gate, the sweep, ``index``, ``cost`` and the
+        returned rows all describe the refined rows - what refine_steps returns was never tested.  The two are independent and may be combined.
 
         Returns the named tuple (path [T x ndof], index [T] int32, cost, n_reachable [T] int32[, node_costs [k * T]]); without an admissible
         path: rows 0, indices -1, cost +inf, and n_reachable shows the first waypoint nothing reaches."""

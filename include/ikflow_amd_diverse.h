@@ -29,6 +29,7 @@
  *   2. when kept < n_keep, every admissible row that was not kept is closer than min_separation to a kept one: its near2 < sep2.
  * Greedy farthest-point selection is not the best subset, but its smallest pairwise distance is at least half of the best subset's (the
  * farthest-first bound), from whichever first pick.
+ * Refined candidates: while a refinement is set on the handle (include/ikflow_amd_refine.h), ikf_generate_diverse selects among LM-refined rows.
  */
 #ifndef IKFLOW_AMD_DIVERSE_H
 #define IKFLOW_AMD_DIVERSE_H

@@ -22,6 +22,7 @@
  * Outputs: path_out[t][:] the chosen row of waypoint t, index_out[t] its candidate r, cost_out[0] the total, reachable_out[t] the number of
  * r with cost[t][r] < +inf (where a path breaks), node_cost_out the node costs in the candidate layout (unweighted).  No path (total +inf):
  * path rows 0, indices -1, cost +inf.
+ * Refined candidates: while a refinement is set on the handle (include/ikflow_amd_refine.h), ikf_generate_path builds its lattice from LM-refined rows.
  */
 #ifndef IKFLOW_AMD_PATH_H
 #define IKFLOW_AMD_PATH_H

@@ -11,6 +11,7 @@
  *   order of a pose = (lower score, then lower candidate index r): a strict total order, so the result is unique
  * Outputs per pose j, i < min(count, n_keep): q_out[j][i][:] the candidate row, score_out[j][i], index_out[j][i] = r; every further slot
  * q = 0, score = +inf, index = -1; count_out[j] = number of admissible candidates.  Every element of every non-null output is written.
+ * Refined candidates: while a refinement is set on the handle (include/ikflow_amd_refine.h), ikf_generate_ranked ranks and returns LM-refined rows.
  */
 #ifndef IKFLOW_AMD_RANK_H
 #define IKFLOW_AMD_RANK_H
