@@ -1078,8 +1078,10 @@ def test_exact_ik_seeded_random_schedules(cfg):
 
 def test_refine_exact_one_round_and_large_compaction():
     """ikf_refine_exact = one _generate_exact_ik_solutions call (:119-247) given its flow output; then the multi-workgroup
-    ordered compaction (n > 32768) through a 100k-pose seeded call whose second round must see exactly the unsolved poses
-    in ascending order."""
+    ordered compaction (n > 32768) through a 100k-pose seeded call whose second round must solve exactly the poses round 0 left.
+    `seen[1]` is NOT the engine's list: Engine.generate_exact rebuilds it with torch.nonzero(valid == 0) from the flags, so what is
+    checked here is round 0's flags and, through the counts and the final flags, the after-effects of the compaction.  The engine's
+    own list is read and compared element for element in tests/test_exact_rounds.py."""
     from ikflow_amd.engine import kinematics_engine_for
     from ikflow_amd.robots import Panda
 
@@ -1095,7 +1097,7 @@ def test_refine_exact_one_round_and_large_compaction():
     both = valid.cpu() & ref_valid
     d1 = (sol.cpu()[both] - ref_sol[both]).abs()
     assert d1.max().item() <= 5e-6 or (int((d1 > 5e-6).sum()) <= 2 and d1.max().item() <= 1e-4), d1.max().item()
-    # 100k poses: round 0 solves the even poses (seed = truth), round 1 must be handed exactly the odd ones, in order
+    # 100k poses: round 0 solves the even poses (seed = truth); the list torch derives from round 0's flags holds exactly the odd ones
     n = 100_000
     eng.reserve_exact(n, 2)
     q_true, poses = reachable_poses(robot, n, 73)
@@ -1111,7 +1113,7 @@ def test_refine_exact_one_round_and_large_compaction():
     solved0 = int(stats[0, 3])
     assert solved0 >= n // 2 and stats[1, 0] == n - solved0
     assert bool((seen[1] % 2 == 1).all()) and seen[1].numel() == n - solved0  # only odd poses are left after round 0
-    assert bool((seen[1][1:] > seen[1][:-1]).all())  # ascending = ordered compaction
+    assert bool((seen[1][1:] > seen[1][:-1]).all())  # ascending (torch.nonzero's order; the kernel's: tests/test_exact_rounds.py)
     assert int(valid.sum()) >= 0.99 * n
 
 
