@@ -1,4 +1,4 @@
-// C-ABI of libikflow_amd.so, the flow (what replaces IKFlowSolver._run_inference, ikflow/ikflow_solver.py:85-110): planner and cluster back-off, the host
+// C-ABI of libikflow_amd.so, the flow (what replaces IKFlowSolver._run_inference, ikflow/ikflow_solver.py:85-110): the planner (flow_plan.h) applied to a handle, the host
 // side of every flow launch sequence, the entries ikf_generate_approx / ikf_flow_forward / ikf_flow_inverse.  See include/ikflow_amd.h for the contract.
 #include "ikf_model.h"
 
@@ -89,46 +89,67 @@ static bool chain_usable(const ikf_model* m, long long nr) {
     if (m->subnets[si].n_x + d.n_pose > 15) return false;
   return true;
 }
+// The pending coupling a subnet leaves behind (its last Linear exists only as partial sums: `slots` sets of them in P)
+static PendingCoupling pending_of(const ikf_model* m, const SubnetPos& p, const float* P, int slots) {
+  const SubnetWeights& w = m->subnets[p.si];
+  PendingCoupling pc{};
+  pc.P = P;
+  pc.b_last = w.b_last;
+  pc.perm_inv = m->d_perm_inv + (size_t)p.b * m->dims.D;
+  pc.slot_stride = m->chunk_rows * IKF_PSTRIDE;
+  pc.slots = slots;
+  pc.which = p.which;
+  pc.n_out = w.n_out;
+  return pc;
+}
+// What the entry phase of the subnet at execution index sidx is given whatever the call: weights, widths, offsets, h_out, x_dst
+static void entry_fixed(const ikf_model* m, int sidx, EntryArgs& e) {
+  const FlowDims& d = m->dims;
+  const SubnetPos p = subnet_at(m->desc.nb_nodes, sidx);
+  const SubnetWeights& w = m->subnets[p.si];
+  e.x_dst = (sidx & 1) ? m->xbuf2 : m->xbuf;
+  e.D = d.D; e.L1 = d.L1; e.clamp = d.clamp;
+  e.x_off = (p.which == 1) ? 0 : d.L1; e.n_x = w.n_x;
+  e.w1t = w.w_first_t; e.w1soft = w.w_soft; e.b1 = w.b_first;
+  e.width = d.width; e.slope = d.slope; e.h_out = m->hA;
+}
+// the finalize kernel behind the last subnet of a chunk: its pending coupling, the linear transform, the limits
+static FinalizeArgs finalize_args(const ikf_model* m, const PendingCoupling& pend, const float* x_src, long long r0, long long nr, int clamp_limits,
+                                  float* d_q_out) {
+  const FlowDims& d = m->dims;
+  FinalizeArgs f{};
+  f.pend = pend; f.x_src = x_src; f.M = (int)nr; f.D = d.D; f.L1 = d.L1; f.ndof = d.ndof; f.clamp = d.clamp;
+  f.M_inv = m->d_Minv; f.b_lin = m->d_blin; f.lo = chain_lo(m); f.hi = chain_hi(m);
+  f.clamp_limits = clamp_limits; f.sigmoid = m->desc.sigmoid_on_output ? 1 : 0; f.q_out = d_q_out + (size_t)r0 * d.ndof;
+  return f;
+}
 static ikf_status chain_table(ikf_model* m) {
   if (m->chain_tab_valid) return IKF_OK;
   const FlowDims& d = m->dims;
   const int NB = m->desc.nb_nodes;
-  const long long rows_pad = m->chunk_rows;
   std::vector<ChainSubnet> tab((size_t)2 * NB);
-  float* xb[2] = {m->xbuf, m->xbuf2};
   PendingCoupling pend{};
   const float* x_src = nullptr;
   for (int sidx = 0; sidx < 2 * NB; ++sidx) {
-    const int b = NB - 1 - sidx / 2, which = 1 + (sidx & 1);
-    const int si = 2 * b + which - 1;
-    const SubnetWeights& w = m->subnets[si];
-    if (frag_image(m, si, 0) == nullptr || frag_image(m, si, 1) == nullptr) return fail(IKF_ERR_HIP, "chain_table: no fragment image");
+    const SubnetPos p = subnet_at(NB, sidx);
+    const SubnetWeights& w = m->subnets[p.si];
+    if (frag_image(m, p.si, 0) == nullptr || frag_image(m, p.si, 1) == nullptr) return fail(IKF_ERR_HIP, "chain_table: no fragment image");
     ChainSubnet& c = tab[sidx];
     memset(&c, 0, sizeof(c));
     EntryArgs& e = c.e;
+    entry_fixed(m, sidx, e);
     e.pend = pend;
-    e.x_src = x_src; e.x_dst = xb[sidx & 1];
-    e.D = d.D; e.L1 = d.L1; e.clamp = d.clamp;
-    e.x_off = (which == 1) ? 0 : d.L1; e.n_x = w.n_x;
-    e.w1t = w.w_first_t; e.w1soft = w.w_soft; e.b1 = w.b_first;
-    e.width = d.width; e.slope = d.slope; e.h_out = m->hA;
+    e.x_src = x_src;
     c.n_in = w.n_x + d.n_pose;
     for (int l = 0; l < 2; ++l) {
       FusedGemmArgs& g = c.g[l];
       g.N = d.width; g.K = d.width; g.slope = d.slope; g.tune = m->tune;
-      g.w_last = w.w_last; g.n_out = w.n_out; g.P_out = m->pbuf; g.p_slot_stride = rows_pad * IKF_PSTRIDE;
-      g.W = w.w_mid[l]; g.bias = w.b_mid[l]; g.Wf = frag_image(m, si, l);
+      g.w_last = w.w_last; g.n_out = w.n_out; g.P_out = m->pbuf; g.p_slot_stride = m->chunk_rows * IKF_PSTRIDE;
+      g.W = w.w_mid[l]; g.bias = w.b_mid[l]; g.Wf = frag_image(m, p.si, l);
     }
     c.g[0].A = m->hA; c.g[0].C = m->hB;   // (the head keeps the first Linear's output in registers: A is unused)
     c.g[1].A = m->hB; c.g[1].C = nullptr;
-    pend = PendingCoupling{};
-    pend.P = m->pbuf;
-    pend.b_last = w.b_last;
-    pend.perm_inv = m->d_perm_inv + (size_t)b * d.D;
-    pend.slot_stride = rows_pad * IKF_PSTRIDE;
-    pend.slots = fused_slots(fused_skinny16_cfg(), d.width);
-    pend.which = which;
-    pend.n_out = w.n_out;
+    pend = pending_of(m, p, m->pbuf, fused_slots(fused_skinny16_cfg(), d.width));
     x_src = e.x_dst;
   }
   IKF_HIP(hipMemcpy(m->d_chain_tab, tab.data(), sizeof(ChainSubnet) * tab.size(), hipMemcpyHostToDevice));
@@ -146,17 +167,9 @@ static ikf_status run_flow_chunk_chain(ikf_model* m, const PoseSource& ps, const
   ChainSync cs{};
   cs.ctl = m->d_chain_ctl; cs.give_up = m->h_give_up; cs.row_tiles = (int)((nr + 15) / 16);
   IKF_HIP(launch_flow_chain16(m->d_chain_tab, 2 * NB, call, cs, d.width, s));
-  const SubnetWeights& w = m->subnets[1];  // the last subnet in execution order: block 0, s2
-  PendingCoupling pend{};
-  pend.P = m->pbuf; pend.b_last = w.b_last; pend.perm_inv = m->d_perm_inv;
-  pend.slot_stride = m->chunk_rows * IKF_PSTRIDE; pend.slots = fused_slots(fused_skinny16_cfg(), d.width);
-  pend.which = 2; pend.n_out = w.n_out;
-  float* xb[2] = {m->xbuf, m->xbuf2};
-  FinalizeArgs f{};
-  f.pend = pend; f.x_src = xb[(2 * NB - 1) & 1]; f.M = (int)nr; f.D = d.D; f.L1 = d.L1; f.ndof = d.ndof; f.clamp = d.clamp;
-  f.M_inv = m->d_Minv; f.b_lin = m->d_blin; f.lo = chain_lo(m); f.hi = chain_hi(m);
-  f.clamp_limits = clamp_limits; f.sigmoid = m->desc.sigmoid_on_output ? 1 : 0; f.q_out = d_q_out + (size_t)r0 * d.ndof;
-  IKF_HIP(launch_flow_finalize(f, s));
+  // the last subnet in execution order (block 0, s2) left its coupling pending and the state in xbuf2 (an odd execution index)
+  const PendingCoupling pend = pending_of(m, subnet_at(NB, 2 * NB - 1), m->pbuf, fused_slots(fused_skinny16_cfg(), d.width));
+  IKF_HIP(launch_flow_finalize(finalize_args(m, pend, m->xbuf2, r0, nr, clamp_limits, d_q_out), s));
   return IKF_OK;
 }
 
@@ -199,26 +212,21 @@ static ikf_status run_flow_chunk_fused(ikf_model* m, const PoseSource& ps, const
   PendingCoupling pend{};
   pend.P = nullptr;
   const float* x_src = d_latent + (size_t)r0 * d.D;
-  float* xb[2] = {m->xbuf, m->xbuf2};
   float* const pb[2] = {m->pbuf, m->pbuf_alt};   // partial sums of even / odd subnets (the same buffer unless a launch both reads and writes them)
   auto entry_args = [&](int sidx, const PendingCoupling& pc, const float* xs) {
-    const int b = NB - 1 - sidx / 2, which = 1 + (sidx & 1);
-    const SubnetWeights& w = m->subnets[2 * b + which - 1];
     EntryArgs e{};
+    entry_fixed(m, sidx, e);
     e.pend = pc;
-    e.x_src = xs; e.x_dst = xb[sidx & 1];
-    e.M = (int)nr; e.D = d.D; e.L1 = d.L1; e.clamp = d.clamp;
-    e.x_off = (which == 1) ? 0 : d.L1; e.n_x = w.n_x;
-    e.ps = ps; e.row0 = r0;
-    e.w1t = w.w_first_t; e.w1soft = w.w_soft; e.b1 = w.b_first;
-    e.width = d.width; e.slope = d.slope; e.h_out = m->hA; e.split_out = split ? 1 : 0;
+    e.x_src = xs;
+    e.M = (int)nr; e.ps = ps; e.row0 = r0;
+    e.split_out = split ? 1 : 0;
     e.split_flag = split ? m->d_split_flag : nullptr;
     e.wt_stores = m->wt_stores < 0 ? (nr <= 2048 ? 1 : 0) : (m->wt_stores >> 1) & 1;
     return e;
   };
   for (int sidx = 0; sidx < 2 * NB; ++sidx) {
-    const int b = NB - 1 - sidx / 2, which = 1 + (sidx & 1);
-    const SubnetWeights& w = m->subnets[2 * b + which - 1];
+    const SubnetPos p = subnet_at(NB, sidx);
+    const SubnetWeights& w = m->subnets[p.si];
     EntryArgs e = entry_args(sidx, pend, x_src);
     if (tail && sidx == 0) { e.zero_words = m->d_arrive; e.n_zero = kArriveWords; }
     FusedGemmArgs g{};
@@ -235,18 +243,10 @@ static ikf_status run_flow_chunk_fused(ikf_model* m, const PoseSource& ps, const
     const bool one_launch = !tail && !split &&
                             (m->fuse_entry == 2 || (m->fuse_entry == 1 && (cfg == fused_skinny32_cfg() || cfg == fused_skinny16_cfg() || cfg == fused_skinny16x16_cfg() || cfg == fused_skinny32v2_cfg()))) &&
                             entry_gemm_ok(cfg, nr, d.width, d.D, pend.P ? pend.n_out : 0) &&
-                            frag_image(m, 2 * b + which - 1, 0) != nullptr;
+                            frag_image(m, p.si, 0) != nullptr;
     if (!one_launch && !entry_done) IKF_HIP(launch_subnet_entry(w.n_x + d.n_pose, e, s));
     entry_done = false;
-    // the pending coupling this subnet leaves behind (its last Linear exists only as partial sums)
-    PendingCoupling mine{};
-    mine.P = pb[sidx & 1];
-    mine.b_last = w.b_last;
-    mine.perm_inv = m->d_perm_inv + (size_t)b * d.D;
-    mine.slot_stride = rows_pad * IKF_PSTRIDE;
-    mine.slots = slots;
-    mine.which = which;
-    mine.n_out = w.n_out;
+    const PendingCoupling mine = pending_of(m, p, pb[sidx & 1], slots);
     float* cur = m->hA;
     float* nxt = m->hB;
     for (int l = 0; l < n_mid; ++l) {
@@ -254,26 +254,25 @@ static ikf_status run_flow_chunk_fused(ikf_model* m, const PoseSource& ps, const
       IKF_HIP(prof_mark(m, s));
       if (split) {
         SplitGemmArgs sg{};
-        sg.A = cur; sg.C = last ? nullptr : nxt; sg.W = m->w_mid_split[(size_t)(2 * b + which - 1) * 3 + l];
-        sg.Wf = m->w_mid_split_frag.empty() ? nullptr : m->w_mid_split_frag[(size_t)(2 * b + which - 1) * 3 + l];
+        sg.A = cur; sg.C = last ? nullptr : nxt; sg.W = m->w_mid_split[(size_t)p.si * 3 + l];
+        sg.Wf = m->w_mid_split_frag.empty() ? nullptr : m->w_mid_split_frag[(size_t)p.si * 3 + l];
         sg.bias = w.b_mid[l]; sg.M = (int)nr; sg.N = d.width; sg.K = d.width; sg.slope = d.slope;
         sg.w_last = w.w_last; sg.n_out = w.n_out; sg.P_out = pb[sidx & 1]; sg.p_slot_stride = rows_pad * IKF_PSTRIDE;
         sg.flag = m->d_split_flag;
         IKF_HIP(launch_split_gemm(last, scfg, sg, s));
       } else {
         g.A = cur; g.C = last ? nullptr : nxt; g.W = w.w_mid[l]; g.bias = w.b_mid[l];
-        g.Wf = frag_image(m, 2 * b + which - 1, l);
+        g.Wf = frag_image(m, p.si, l);
         if (l == 0 && one_launch) IKF_HIP(launch_entry_gemm(w.n_x + d.n_pose, last, cfg, e, g, s));
         else if (last && tail && sidx + 1 < 2 * NB) {
           // subnet sidx+1's entry phase rides in this launch's tail: its pending coupling is what this launch produces, its
           // state source is the state this subnet's entry phase published
-          const int b2 = NB - 1 - (sidx + 1) / 2, which2 = 1 + ((sidx + 1) & 1);
           const EntryArgs e2 = entry_args(sidx + 1, mine, e.x_dst);
           TailSync ts{};
           ts.arrive = m->d_arrive;
           ts.target = (unsigned)(tails_done + 1) * (unsigned)fused_tail_col_tiles(cfg, d.width);
           ts.give_up = m->h_give_up;
-          ts.n_in = m->subnets[2 * b2 + which2 - 1].n_x + d.n_pose;
+          ts.n_in = e2.n_x + d.n_pose;
           IKF_HIP(launch_flow_gemm_tail(cfg, g, e2, ts, s));
           ++tails_done;
           entry_done = true;
@@ -285,11 +284,7 @@ static ikf_status run_flow_chunk_fused(ikf_model* m, const PoseSource& ps, const
     pend = mine;
     x_src = e.x_dst;
   }
-  FinalizeArgs f{};
-  f.pend = pend; f.x_src = x_src; f.M = (int)nr; f.D = d.D; f.L1 = d.L1; f.ndof = d.ndof; f.clamp = d.clamp;
-  f.M_inv = m->d_Minv; f.b_lin = m->d_blin; f.lo = chain_lo(m); f.hi = chain_hi(m);
-  f.clamp_limits = clamp_limits; f.sigmoid = m->desc.sigmoid_on_output ? 1 : 0; f.q_out = d_q_out + (size_t)r0 * d.ndof;
-  IKF_HIP(launch_flow_finalize(f, s));
+  IKF_HIP(launch_flow_finalize(finalize_args(m, pend, x_src, r0, nr, clamp_limits, d_q_out), s));
   return IKF_OK;
 }
 
@@ -345,20 +340,7 @@ static ikf_status run_flow_chunk_unfused(ikf_model* m, const PoseSource& ps, con
   return IKF_OK;
 }
 
-// ---- which form runs which rows of a batch -------------------------------------------------------------------------------------------
-// Three forms compute the same function: the per-layer kernels (any shape), the row-owner launch (a round of CUs x 16 rows costs the same
-// whatever part of it is used) and the cluster form (G = 8 / 4 / 2: <= 512 / 1024 / 2048 rows at a fixed cost each).  A batch is cut into
-// consecutive chunks by the cheapest plan under the measured costs of the released 12-block shape on 256 CUs (ms per launch,
-// tools/rowowner_ab.py, profiles/r04_rowowner_ab.jsonl) - the ratios, not the absolute values, decide, and they hold for any depth:
-//   row-owner round 2.82;  cluster 0.285 / 0.335 / 0.485 / 0.82 / 1.51 for G = 32 / 16 / 8 / 4 / 2 (<= 128 / 256 / 512 / 1024 / 2048 rows; r05);
-//   per-layer 0.272 / 0.305 / 0.316 / 0.367 / 0.52 / 0.71 / 1.04 / 1.75 / 2.56 / 2.62 / 3.20 up to 1 / 16 / 64 / 128 / 256 / 512 / 1024 /
-//   2048 / 2560 / 3072 / 4096 rows (+ 0.10 beside the resident-row forms: another weight image, see plan_tail);  + 0.01 per extra chunk.
-// e.g. 1 .. 128 -> cluster 32; 200 -> cluster 16; 512 -> cluster 8; 600 -> cluster 4; 1536 -> cluster 4 (1024) + cluster 8 (512); 2304 -> cluster 2 (2048) + per-layer (256);
-// 3400 -> one row-owner round; 4096 k + r -> k rounds in one row-owner launch + the plan of r.
-struct FlowChunk {
-  int form;         // 0 per-layer, 1 row-owner, 2 / 4 / 8 cluster members
-  long long rows;
-};
+// ---- which form runs which rows of a batch: flow_plan.h decides (plan_rows, ClusterBackoff); here is what a handle brings to it ----
 static bool rowowner_allowed(const ikf_model* m) {
   return m->ro_stream != nullptr && m->ro_mode != 0 && m->precision == 0 && m->loaded &&
          (m->ro_mode == 1 || (m->gemm_variant < 0 && m->tile_cfg < 0 && m->fuse_tail == 0));
@@ -369,11 +351,12 @@ static bool rowowner_allowed(const ikf_model* m) {
 // Rare path (a 5 ms stall has just happened): one device synchronisation and a copy of a few KB.
 static bool cluster_tagged_local_misplaced(ikf_model* m) {
   DeviceGuard guard(m->device);
-  if (guard.err != hipSuccess || m->cl_tl_words == nullptr) return false;
+  const unsigned* words = cluster_tagged_xcc_words(m);
+  if (guard.err != hipSuccess || words == nullptr) return false;
   const int n_rt = m->cl_tl_nrt, G = m->cl_tl_G;
   std::vector<unsigned> w((size_t)n_rt * 32, 0xffffffffu);
   if (hipDeviceSynchronize() != hipSuccess) return false;
-  if (hipMemcpy(w.data(), m->cl_tl_words, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return false;
+  if (hipMemcpy(w.data(), words, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return false;
   unsigned seq = 0;
   bool any = false;
   for (int rt = 0; rt < n_rt; ++rt)
@@ -395,8 +378,6 @@ static bool cluster_tagged_local_misplaced(ikf_model* m) {
   }
   return false;
 }
-static const long long kClusterFirstPause = 16, kClusterMaxPause = 65536;
-static const int kClusterCleanStreak = 64;
 // folds a pending give-up word into the handle's state (no side effect otherwise)
 static void cluster_fold_give_up(ikf_model* m) {
   if (!m->h_cl_give_up || *m->h_cl_give_up == 0) return;
@@ -404,133 +385,28 @@ static void cluster_fold_give_up(ikf_model* m) {
   int why = *m->h_cl_give_up;
   *m->h_cl_give_up = 0;
   if (why == 1 && m->cl_local != 0 && m->cl_tl_nrt > 0 && cluster_tagged_local_misplaced(m)) why = 2;
-  ++m->cl_repairs;
-  m->cl_clean = 0;
-  m->cl_tag_dirty = true;                        // (whichever hand-over it was: the tagged buffers are re-created before their next use)
-  if (why == 2) m->cl_local = 0;                 // a member of the XCD-local form met a peer on another XCD: back to the spread form
-  else {                                         // a wait ran out: somebody else held CUs - sit out, twice as long as the last time
-    m->cl_backoff = m->cl_backoff == 0 ? kClusterFirstPause : (m->cl_backoff * 2 < kClusterMaxPause ? m->cl_backoff * 2 : kClusterMaxPause);
-    m->cl_pause = m->cl_backoff;
-  }
+  m->cl_tag_dirty = true;                            // (whichever hand-over it was: the tagged buffers are re-created before their next use)
+  if (m->cl_back.give_up(why)) m->cl_local = 0;      // a member of the XCD-local form met a peer on another XCD: back to the spread form
 }
-static bool cluster_allowed_now(const ikf_model* m) {
-  if (m->ro_stream == nullptr || m->cl_mode == 0 || m->precision != 0 || !m->loaded || m->cl_pause > 0) return false;
+// everything but the pause: the handle has the form and its settings leave the choice to the planner
+static bool cluster_enabled(const ikf_model* m) {
+  if (m->ro_stream == nullptr || m->cl_mode == 0 || m->precision != 0 || !m->loaded) return false;
   return m->cl_mode == 1 || (m->gemm_variant < 0 && m->tile_cfg < 0 && m->fuse_tail == 0 && m->ro_mode != 0);
 }
-// the planner's question, asked once per plan: counts the pause down and the clean streak up
-static bool cluster_allowed(ikf_model* m) {
-  cluster_fold_give_up(m);
-  if (m->cl_used_last && m->cl_pause == 0 && m->cl_backoff != 0 && ++m->cl_clean >= kClusterCleanStreak) m->cl_backoff = 0;
-  m->cl_used_last = false;
-  if (m->cl_pause > 0) {
-    --m->cl_pause;
-    return false;
-  }
-  return cluster_allowed_now(m);
-}
-static double per_layer_cost(long long rows_on_256) {
-  static const struct { long long rows; double ms; } t[] = {{1, 0.272}, {16, 0.305}, {64, 0.316}, {128, 0.367}, {256, 0.52}, {512, 0.71}, {1024, 1.04},
-                                                            {2048, 1.75}, {2560, 2.56}, {3072, 2.62}, {4096, 3.20}};
-  for (const auto& e : t)
-    if (rows_on_256 <= e.rows) return e.ms;
-  return 3.20 * (double)rows_on_256 / 4096.0;
-}
-// cheapest plan for `rows` rows below one row-owner round; returns its cost, appends its chunks.  Only the forms of G <= 8 (>= 512 rows
-// per launch) are taken as a full launch in front of a rest - the small forms only for a whole (rest of a) tail - and results are memoised
-// by the remaining row count: a handful of states, a few microseconds per call (an unbounded search over 128-row pieces is exponential).
-struct TailPlan {
-  double cost;
-  std::vector<FlowChunk> chunks;
-};
-// The per-layer kernels read their own weight images (2 x 203 MB beside the row-owner stream's 203 MB; the Infinity Cache holds 256 MB): next
-// to a chunk of another form (mixed), or on a handle whose other calls use the cluster form (cl), they find the cache holding the other
-// image and leave it holding theirs - measured + 0.07 ... 0.1 ms on a 513- / 1025- / 2049-row call whose last row went to them.  They are
-// charged for it, so that where the resident-row forms are allowed EVERY size reads one image (1 row alone: 0.273 against cluster32's 0.277;
-// an exact-IK call on one pose runs rounds of 1, 3, 10 rows); they remain what a handle without those forms, or another shape, runs.
-static const TailPlan& plan_tail(long long rows, long long round, bool ro, bool cl, bool mixed, std::unordered_map<long long, TailPlan>& memo) {
-  auto it = memo.find(rows);
-  if (it != memo.end()) return it->second;
-  TailPlan best{0.0, {}};
-  if (rows > 0) {
-    const long long on256 = rows * 4096 / round;   // the cost tables are in rows of a 256-CU chip
-    best = TailPlan{per_layer_cost(on256) + ((mixed || cl) ? 0.10 : 0.0), {{0, rows}}};
-    if (ro && 2.82 < best.cost) best = TailPlan{2.82, {{1, rows}}};
-    if (cl) {
-      static const struct { int G; double ms; } forms[] = {{32, 0.285}, {16, 0.335}, {8, 0.485}, {4, 0.82}, {2, 1.51}};   // (r05: tagged hand-over for G <= 16)
-      for (const auto& f : forms) {
-        const long long cap = (round / IKF_RO_ROWS) / f.G * IKF_RO_ROWS;   // rows of a full grid of this form: whole tiles, at most one workgroup per CU
-        if (cap <= 0) continue;
-        if (rows <= cap) {                   // the whole tail in one launch of this form
-          if (f.ms < best.cost) best = TailPlan{f.ms, {{f.G, rows}}};
-        } else if (f.G <= 8) {               // a full launch of this form, then the plan of what is left
-          const TailPlan rest = plan_tail(rows - cap, round, ro, cl, true, memo);   // (by value: the map may rehash)
-          const double c = f.ms + 0.01 + rest.cost;
-          if (c < best.cost) {
-            best = TailPlan{c, {{f.G, cap}}};
-            best.chunks.insert(best.chunks.end(), rest.chunks.begin(), rest.chunks.end());
-          }
-        }
-      }
-    }
-  }
-  return memo.emplace(rows, std::move(best)).first->second;
-}
-// (host logic only - no device, no handle: ikf_plan_describe_for runs it in the CPU tests.  ro / cl: the form may be used at all;
-// ro_mode / cl_mode 1: forced; ro_min_tail >= 0: the probes' explicit threshold for the last partial round)
-static std::vector<FlowChunk> plan_rows(long long rows, int n_cu, bool ro, bool cl, int ro_mode, int cl_mode, long long ro_min_tail) {
-  std::vector<FlowChunk> plan;
-  if (rows <= 0 || n_cu <= 0) return plan;
-  const long long round = (long long)n_cu * IKF_RO_ROWS;
-  if (ro && ro_mode == 1) return {{1, rows}};
-  if (cl && cl_mode == 1 && rows <= round / 2) {  // forced: one launch of the widest form whose grid fits
-    for (int g = 32; g >= 2; g /= 2)
-      if (rows <= (long long)(n_cu / g) * IKF_RO_ROWS) return {{g, rows}};
-  }
-  long long full = ro ? rows / round * round : 0;
-  if (!ro && cl && rows > round) {
-    // no row-owner launch to take the full rounds: whole 2-member cluster launches (the cheapest form per row) are peeled off here, one
-    // chunk each, and plan_tail only sees what is left below a round (its recursion is one level per full launch)
-    const long long cap2 = (round / IKF_RO_ROWS) / 2 * IKF_RO_ROWS;
-    while (cap2 > 0 && rows - full > round) {
-      plan.push_back({2, cap2});
-      full += cap2;
-    }
-  }
-  const bool peeled = !ro && full > 0;
-  std::vector<FlowChunk> tail;
-  if (rows - full > 0) {
-    if (ro && ro_min_tail >= 0) {
-      if (rows - full >= ro_min_tail) tail = {{1, rows - full}};
-      else tail = {{0, rows - full}};
-    } else {
-      std::unordered_map<long long, TailPlan> memo;
-      tail = plan_tail(rows - full, round, ro, cl, full > 0, memo).chunks;
-    }
-  }
-  if (full > 0 && !peeled) plan.push_back({1, full});
-  for (const FlowChunk& c : tail) {
-    if (!plan.empty() && plan.back().form == 1 && c.form == 1) plan.back().rows += c.rows;   // the partial round rides in the same launch
-    else plan.push_back(c);
-  }
-  return plan;
-}
-// `consume`: this plan is about to run (it counts against a pause of the cluster form); the describing entry points pass false
+// `consume`: this plan is about to run (it counts against a pause of the cluster form and towards its clean streak); the describing entry
+// points pass false and only look at the pause
 static std::vector<FlowChunk> plan_flow(ikf_model* m, long long rows, bool consume = false) {
   if (rows <= 0) return {};
   cluster_fold_give_up(m);
-  const bool ro = rowowner_allowed(m), cl = consume ? cluster_allowed(m) : cluster_allowed_now(m);
+  const bool may = consume ? m->cl_back.ask() : !m->cl_back.paused();
+  const bool ro = rowowner_allowed(m), cl = may && cluster_enabled(m);
   std::vector<FlowChunk> plan = plan_rows(rows, m->n_cu, ro, cl, m->ro_mode, m->cl_mode, m->ro_min_tail);
-  if (consume)
-    for (const FlowChunk& c : plan) m->cl_used_last = m->cl_used_last || c.form >= 2;
-  return plan;
-}
-static std::string plan_text(const std::vector<FlowChunk>& plan) {
-  std::string out;
-  for (const FlowChunk& c : plan) {
-    if (!out.empty()) out += " ";
-    out += (c.form == 0 ? std::string("perlayer") : c.form == 1 ? std::string("rowowner") : "cluster" + std::to_string(c.form)) + ":" + std::to_string(c.rows);
+  if (consume) {
+    bool cluster_chunk = false;
+    for (const FlowChunk& c : plan) cluster_chunk = cluster_chunk || c.form >= 2;
+    m->cl_back.used(cluster_chunk);
   }
-  return out;
+  return plan;
 }
 static RoArgs rowowner_args(ikf_model* m, const PoseSource& ps, const float* d_latent, long long r0, long long nr, int clamp_limits, float* d_q_out) {
   const FlowDims& d = m->dims;
@@ -567,7 +443,7 @@ static ikf_status run_flow_cluster(ikf_model* m, int G, const PoseSource& ps, co
   const bool local = m->cl_local != 0 && cluster_local_form(G) && cluster_grid(c.n_rt, G, true) <= (unsigned)m->n_cu;
   c.give_up = m->h_cl_give_up;
   if (tagged) {
-    unsigned* const abort_t = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(m->cl_sync_t.p) + m->cl_sync_t_bytes - 128);
+    unsigned* const abort_t = cluster_tagged_abort_word(m);
     if (m->cl_tag_dirty) {
       IKF_HIP(cluster_tagged_init(m->cl_xbuf_t, cluster_xbuf_floats((int)(m->cl_rows / IKF_RO_ROWS)), m->cl_sync_t, m->cl_sync_t_bytes - 128, abort_t, s));
       m->cl_tag_dirty = false;
@@ -578,12 +454,11 @@ static ikf_status run_flow_cluster(ikf_model* m, int G, const PoseSource& ps, co
     c.abort_word = abort_t;
     c.test_far = local ? m->cl_far_next : 0;   // (variant 191: honoured by the tagged form's placement check too)
     if (local) m->cl_far_next = 0;
-    // the members' placement words sit behind the partial sums of the largest launch (the epoch-word form's flag area, unused here)
-    c.xcc_words = reinterpret_cast<unsigned*>(m->cl_sync_t.p) + (size_t)(m->cl_rows / IKF_RO_ROWS) * 8 * 256;
+    c.xcc_words = cluster_tagged_xcc_words(m);
     m->cl_launch_seq = (m->cl_launch_seq + 1) & 0xffffffu;
     if (m->cl_launch_seq == 0xffffffu) m->cl_launch_seq = 0;
     c.launch_seq = m->cl_launch_seq;
-    if (local) { m->cl_tl_nrt = c.n_rt; m->cl_tl_G = G; m->cl_tl_words = c.xcc_words; }
+    if (local) { m->cl_tl_nrt = c.n_rt; m->cl_tl_G = G; }
     IKF_HIP(prof_mark(m, s));
     IKF_HIP(launch_flow_cluster_tagged(c, G, s, m->cl_drop_next, local));
   } else {
@@ -632,13 +507,13 @@ extern "C" int ikf_cluster_local(ikf_model* m) {
 extern "C" int64_t ikf_cluster_repairs(ikf_model* m) {
   if (!m) return 0;
   cluster_fold_give_up(m);
-  return (int64_t)m->cl_repairs;
+  return (int64_t)m->cl_back.repairs();
 }
 // calls the cluster form still sits out after a wait of one of its launches ran out (0: in use / never paused)
 extern "C" int64_t ikf_cluster_backoff(ikf_model* m) {
   if (!m) return 0;
   cluster_fold_give_up(m);
-  return (int64_t)m->cl_pause;
+  return (int64_t)m->cl_back.pause_left();
 }
 extern "C" const char* ikf_dominant_kernel_for(const ikf_model* m, int64_t rows) {
   if (m && rows > 0) {

@@ -191,6 +191,7 @@ ikf_status ikf::ensure_cluster_scratch(ikf_model* m, long long rows) {
   m->cl_xbuf_t.release();
   m->cl_sync_t.release();
   m->cl_rows = 0;
+  m->cl_tl_nrt = m->cl_tl_G = 0;   // (the placement words of the last tagged + XCD-local launch went with cl_sync_t: a give-up folded from here on reads nothing)
   const long long cap = (long long)m->n_cu / 2 * IKF_RO_ROWS;   // the largest chunk the form takes (G = 2)
   const int tiles = (int)((cap + IKF_RO_ROWS - 1) / IKF_RO_ROWS);
   const size_t sync_bytes = cluster_sync_bytes(tiles, 8);   // (sized for G = 8 on every tile: 4.6 KB per tile)
@@ -204,6 +205,16 @@ ikf_status ikf::ensure_cluster_scratch(ikf_model* m, long long rows) {
   m->cl_tag_dirty = true;   // (created by the first launch that uses them, on its stream)
   m->cl_rows = cap;
   return IKF_OK;
+}
+// The tagged buffers' abort word: the last 128-byte line of cl_sync_t (what is in front of it is created as parity-1 floats).
+unsigned* ikf::cluster_tagged_abort_word(const ikf_model* m) {
+  if (m->cl_sync_t.p == nullptr) return nullptr;
+  return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(m->cl_sync_t.p) + m->cl_sync_t_bytes - 128);
+}
+// The members' placement words [row tile][32]: behind the partial sums of the largest launch (the epoch-word form's flag area, unused here).
+unsigned* ikf::cluster_tagged_xcc_words(const ikf_model* m) {
+  if (m->cl_sync_t.p == nullptr) return nullptr;
+  return reinterpret_cast<unsigned*>(m->cl_sync_t.p) + (size_t)(m->cl_rows / IKF_RO_ROWS) * 8 * 256;
 }
 
 extern "C" ikf_status ikf_reserve(ikf_model* m, int64_t max_rows) {

@@ -147,8 +147,8 @@ static hipError_t build_rowowner_stream_hip(ikf_model* m, const std::vector<int>
   if ((e = m->d_ro_sub.ensure(n_sub)) != hipSuccess) return e;
   std::vector<RoSubnet> tab(n_sub);
   for (int sidx = 0; sidx < n_sub; ++sidx) {
-    const int b = NB - 1 - sidx / 2, which = 1 + (sidx & 1);
-    const SubnetWeights& w = m->subnets[2 * b + which - 1];
+    const auto [b, which, si] = subnet_at(NB, sidx);
+    const SubnetWeights& w = m->subnets[si];
     if ((e = launch_rowowner_pack(w, m->ro_stream + (size_t)sidx * rowowner_subnet_floats(), nullptr)) != hipSuccess) return e;
     RoSubnet& r = tab[sidx];
     memset(&r, 0, sizeof(r));
@@ -409,8 +409,7 @@ extern "C" ikf_status ikf_load_weights(ikf_model* m, const ikf_tensor* tensors, 
   ikf_status fst = build_rowowner_stream(m, perm_host, perm_fwd);
   if (fst != IKF_OK) return fst;
   m->loaded = true;
-  m->cl_pause = m->cl_backoff = 0;
-  m->cl_clean = 0;
+  m->cl_back.forget();
   if (m->precision == 1) {
     ikf_status sst = build_split_weights(m);  // refusal: precision falls back to f32, the handle stays usable
     if (sst != IKF_OK) return sst;

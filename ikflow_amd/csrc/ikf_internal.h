@@ -12,6 +12,7 @@
 #include "world_math.h"
 #include "sweep_math.h"
 #include "refine_math.h"
+#include "flow_plan.h"  // IKF_RO_ROWS, the planner and the cluster back-off (host arithmetic, no HIP)
 
 namespace ikf {
 
@@ -320,7 +321,6 @@ hipError_t launch_flow_cluster_tagged(const RcArgs& c, int G, hipStream_t s, int
 hipError_t cluster_placement_census(int n_cu, bool* groups_of_8_share_an_xcd);   // one tiny launch: where workgroup b of a grid lands
 bool cluster_local_form(int G);                          // G = 4 / 8 / 16: a form with every member of a row tile on one XCD exists
 unsigned cluster_grid(int n_rt, int G, bool local);      // workgroups of a launch (the local form pads to whole groups of 8 row tiles)
-constexpr int IKF_RO_ROWS = 16;                       // rows per workgroup
 size_t rowowner_subnet_floats();                        // floats of one subnet's stream image
 size_t rowowner_stream_floats(int n_sub);               // whole image incl. the ring's lead padding
 bool rowowner_shape_ok(const FlowDims& d, int n_sub);

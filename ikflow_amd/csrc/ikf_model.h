@@ -124,20 +124,12 @@ struct ikf_model {
   bool cl_tag_dirty = false;
   PinnedBuf<int> h_cl_give_up;    // pinned, device-visible
   int cl_drop_next = 0;           // tests: the next cluster launch runs one workgroup short (ikf_set_gemm_variant 188): its tile's waits run out
-  long long cl_repairs = 0;       // give-ups seen so far (ikf_cluster_repairs)
-  // A wait that ran out means a peer was not resident - another process's kernel held CUs just then.  That tenant may be gone a second
-  // later, so the form is not switched off for good: it sits out cl_pause plans (ikf_generate_* calls), 16 after the first give-up and
-  // twice as many after every further one (at most 65536); kClusterCleanStreak calls of the form in a row without a give-up forget the
-  // history.  ikf_cluster_backoff reports what is left of the pause.
-  long long cl_pause = 0;         // plans the form still sits out
-  long long cl_backoff = 0;       // length of the last pause (0: no give-up on record)
-  int cl_clean = 0;               // cluster calls since the last give-up
-  bool cl_used_last = false;      // the previous plan contained a cluster launch
-  int cl_census_ok = -1;          // the placement census at load: workgroups b and b + 8 k share an XCD (1) or not (0); -1 not asked
+  ClusterBackoff cl_back;         // give-ups seen so far and the pause they cost (flow_plan.h; ikf_cluster_repairs / ikf_cluster_backoff)
+  int cl_census_ok = -1;         // the placement census at load: workgroups b and b + 8 k share an XCD (1) or not (0); -1 not asked
   int cl_far_next = 0;            // tests (ikf_set_gemm_variant 191): the next XCD-local launch's workgroup 0 publishes a wrong XCC_ID
   unsigned cl_launch_seq = 0;     // tagged + XCD-local launches carry a 24-bit sequence number in their placement words (RcArgs::launch_seq)
-  int cl_tl_nrt = 0, cl_tl_G = 0; // row tiles / members of the most recent tagged + XCD-local launch (whose placement words a give-up makes the host read)
-  unsigned* cl_tl_words = nullptr;
+  int cl_tl_nrt = 0, cl_tl_G = 0; // row tiles / members of the most recent tagged + XCD-local launch (whose placement words a give-up makes the host
+                                  // read: cluster_tagged_xcc_words); 0 again when the buffers are released
   int cl_local = 1;               // G = 4 / 8 / 16: the form with a row tile's members on one XCD (hand-over through its L2); 0 after a member met a
                                   // peer on another XCD (placement is verified in the launch, never assumed) or by ikf_set_gemm_variant 189
 
@@ -210,7 +202,16 @@ struct ikf_model {
   double last_event_overhead_ms = 0.0;
 };
 
-static const int kArriveWords = 256;  // >= row tiles of any launch that hands over inside the launch (<= 256 tiles)
+// The inverse pass runs the coupling blocks last to first, s1 then s2 of each: the subnet at execution index sidx of 2 * NB
+struct SubnetPos {
+  int b, which, si;  // coupling block, 1 = s1 / 2 = s2, index into ikf_model::subnets
+};
+static inline SubnetPos subnet_at(int NB, int sidx) {
+  const int b = NB - 1 - sidx / 2, which = 1 + (sidx & 1);
+  return {b, which, 2 * b + which - 1};
+}
+
+static const int kArriveWords = 256; // >= row tiles of any launch that hands over inside the launch (<= 256 tiles)
 static const size_t kProfMaxPairs = 8192;
 static inline hipError_t prof_mark(ikf_model* m, hipStream_t s) {
   if (!m->prof_on || m->prof_used >= 2 * kProfMaxPairs) return hipSuccess;
@@ -280,6 +281,8 @@ ikf_status ensure_scratch(ikf_model* m, long long rows);
 ikf_status ensure_exact_rows(ikf_model* m, long long rows);
 ikf_status ensure_exact(ikf_model* m, long long poses, long long rows);
 ikf_status ensure_cluster_scratch(ikf_model* m, long long rows);
+unsigned* cluster_tagged_abort_word(const ikf_model* m);   // where the tagged hand-over's words sit in cl_sync_t (null: no buffer)
+unsigned* cluster_tagged_xcc_words(const ikf_model* m);
 ikf_status build_split_weights(ikf_model* m);
 ikf_status build_frag_weights(ikf_model* m);
 ikf_status check_ready(ikf_model* m, const char* fn);
