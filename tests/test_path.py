@@ -1,6 +1,7 @@
 """Path IK on the GPU (include/ikflow_amd_path.h; ikflow_amd/csrc/path_kernels.hip, path_math.h, api_path.hip): the lattice against sequential numpy
 float32 arithmetic on the engine's own node costs (bit for bit: every step of the search is rounded on its own), the node costs against the
-ranking's row scores (the same function), the "no path" outputs, null outputs, the flow + search call in both latent forms against
+ranking's row scores (the same function), every chain size (4 .. 8 joints) and every span of the lattice workgroup, ties between slices and waves
+(constructed: bit-equal candidates), the "no path" outputs, null outputs, the flow + search call in both latent forms against
 generate_ik_solutions + ikf_path_search, status codes, ikf_reserve_path, and IKFlowSolver.generate_ik_path end to end.
 
 Every call goes through _path(): outputs are windows inside sentinel-filled buffers with guard rows in front and behind (the scheme of
@@ -102,7 +103,23 @@ CASES = {
     "chunk": (CHUNK, 5, "panda", {}),
     "chunk+1": (CHUNK + 1, 5, "panda", {}),
     "2chunk+1": (2 * CHUNK + 1, 5, "panda", {}),
+    # every span: kp = path_span(k) = 2, 4, 16, 64 (four slices in four waves), 128 (two slices, merged through LDS) and 256 (one slice, no merge;
+    # at k = 129 and 255 with dead destinations) ...
+    "T5_k2": (5, 2, "panda", {}),
+    "T5_k4": (5, 4, "panda", {}),
+    "T5_k16": (5, 16, "panda", {}),
+    "T5_k63": (5, 63, "panda", {}),
+    "T5_k65": (5, 65, "panda", {}),
+    "T5_k127": (5, 127, "panda", {}),
+    "T5_k128": (5, 128, "panda", {}),
+    "T5_k129": (5, 129, "panda", {}),
+    "T5_k255": (5, 255, "panda", {}),
+    # ... and the walk back across a chunk of back-pointers at kp = 128 and 256
+    "T66_k65": (CHUNK + 2, 65, "panda", {}),
+    "T66_k129": (CHUNK + 2, 129, "panda", {}),
+    "ndof4": (65, 33, "syn4p", {}),     # k_path_lattice<4 .. 8, false>: a prismatic chain at 4 and 5 joints, a revolute one at 6
     "ndof5": (65, 33, "syn5p", {}),
+    "ndof6": (65, 33, "syn6r", {}),
     "ndof8": (65, 33, "fetch", {}),
     "q_start": (65, 33, "panda", dict(q_start=True)),
     "step_gate": (65, 33, "panda", dict(max_step=0.12)),   # (forbids edges of the free lattice's path; at 0.1 no path is left)
@@ -136,6 +153,63 @@ def test_lattice_equals_sequential_numpy_float32_on_the_engines_node_costs(case)
     if case == "T65_k33":   # the same call on another stream
         again = _path(eng, poses, q, k, opt, stream=torch.cuda.Stream(device=DEV))
         assert all(PH.same_bits(out[n], again[n]) for n in OUTPUTS)
+
+
+# ---- 1b. ties between slices and waves ---------------------------------------------------------------------------------------------------------------
+TIE_T = 9
+# k = 6 and 17: the duplicates sit in slices of one wave (merged by __shfl_xor); 33: in different waves (kp = 64, merged through LDS); 65 and 128:
+# kp = 128, the two slices of a destination; 129 and 256: kp = 256, one slice - the tie is path_relax's own.  The end of the path is path_argmin's.
+TIE_KS = (6, 17, 33, 65, 128, 129, 256)
+TIE_SEEDS = {}   # k -> seed of _inputs where TIE_T + k does not serve (see the condition in the test)
+
+
+def _tie_inputs(k):
+    """_inputs at (TIE_T, k) with, at every waypoint, candidate 0's row copied onto candidate k - 1 and candidate 1's row onto candidate k / 2:
+    the copies have bit-equal node costs and bit-equal edge sums to every destination."""
+    orob = H.kin_robots("panda")[1]
+    poses, q, q_true = _inputs(orob, TIE_T, k, seed=TIE_SEEDS.get(k, TIE_T + k))
+    g = q.reshape(k, TIE_T, -1).clone()
+    g[k - 1] = g[0]
+    g[k // 2] = g[1]
+    return poses, g.reshape(k * TIE_T, -1).contiguous(), q_true
+
+
+@pytest.mark.parametrize("k", TIE_KS)
+def test_ties_between_slices_and_waves_go_to_the_lower_index(k):
+    """What tests/test_path_math_host.py::test_ties_go_to_the_lower_index proves of path_before, on the GPU, where the tie is resolved inside a
+    slice, by __shfl_xor, through s_part_c / s_part_j and by path_argmin at the end: two pairs of bit-equal candidates per waypoint.  The result is
+    the numpy lattice's (np.argmin: the first minimum), and neither copy is ever chosen.  Condition, checked with the numpy lattice on the
+    engine's node costs: the path goes through candidate 0 or 1 somewhere - there the copy ties with it."""
+    T = TIE_T
+    eng = _eng("panda")
+    poses, q, _ = _tie_inputs(k)
+    opt = _popt()
+    out = _path(eng, poses, q, k, opt)
+    node = out["node"].reshape(k, T)
+    assert PH.same_bits(node[k - 1], node[0]) and PH.same_bits(node[k // 2], node[1]) and np.isfinite(node).all()
+    index = _check_against_dp(out, q, T, k, opt, what=f"ties k {k}")
+    n_tied = int(np.isin(index, (0, 1)).sum())
+    print(f"ties k {k}: the path takes candidate 0 or 1 at {n_tied} of {T} waypoints, index {index.tolist()}")
+    assert n_tied >= 1, f"k {k}: the path never takes a duplicated candidate - the case does not test the tie (another seed: TIE_SEEDS)"
+    assert not np.isin(out["index"], (k - 1, k // 2)).any(), f"k {k}: a copy was chosen over its lower-indexed original: {out['index'].tolist()}"
+
+
+@pytest.mark.parametrize("k", TIE_KS)
+def test_a_lattice_of_equal_candidates_takes_candidate_zero_everywhere(k):
+    """Every candidate of a waypoint is the same row, and q_start is set: every predecessor of every node ties, and so do all k ends."""
+    T = TIE_T
+    orob = H.kin_robots("panda")[1]
+    eng = _eng("panda")
+    poses, q, q_true = _inputs(orob, T, k, seed=T + k)
+    g = q.reshape(k, T, -1)
+    q = g[:1].expand(k, T, g.shape[2]).reshape(k * T, -1).contiguous()
+    q_start = (q_true[0] + 0.05).contiguous()
+    opt = _popt()
+    out = _path(eng, poses, q, k, opt, q_start)
+    assert np.isfinite(out["node"]).all() and np.isfinite(out["cost"][0])
+    _check_against_dp(out, q, T, k, opt, q_start, what=f"equal candidates k {k}")
+    assert (out["index"] == 0).all(), out["index"].tolist()
+    assert (out["reach"] == k).all(), out["reach"].tolist()
 
 
 # ---- 2. no path; null outputs ----------------------------------------------------------------------------------------------------------------------
@@ -195,6 +269,30 @@ def test_shared_latent_equals_the_expanded_latent_and_the_two_step_route(T, k):
     assert all(PH.same_bits(shared[n], two_step[n]) for n in OUTPUTS)
     _check_against_dp(shared, rows, T, k, opt, what=f"tiny T {T} k {k}")
     other = _path(eng, poses, None, k, opt, latent=H.latents(k * T, lay.dim, 13), shared=False)    # (a latent per node is another lattice)
+    assert not PH.same_bits(other["node"], shared["node"])
+
+
+EXPAND_MAX_THREADS = 8192 * 256   # launch_path_expand_latent caps the grid at 8192 workgroups of 256: beyond it a thread copies a second element
+
+
+def test_shared_latent_equals_the_expanded_latent_beyond_the_expansion_grid():
+    """k = 256 and the smallest T with k * T * D > 8192 * 256: k_path_expand_latent's grid-stride loop takes a second trip.  An element it left
+    out would keep what the handle's latent buffer held, and the flow's rows, the node costs and the path would differ from the expanded call's."""
+    s, robot, lay, sd = _solver("tiny")
+    eng = s.engine(DEV)
+    k = 256
+    T = EXPAND_MAX_THREADS // (k * lay.dim) + 1
+    assert k * (T - 1) * lay.dim <= EXPAND_MAX_THREADS < k * T * lay.dim
+    _, poses = H.reachable_poses(robot, T, 31)
+    poses = poses.float()
+    L = H.latents(k, lay.dim, 32)
+    expanded = L[:, None, :].expand(k, T, lay.dim).reshape(k * T, lay.dim).contiguous()
+    opt = _popt(limits=True, max_step=3.0)
+    other = _path(eng, poses, None, k, opt, latent=H.latents(k, lay.dim, 33), shared=True)   # (the handle's buffer now holds OTHER latents, expanded)
+    shared = _path(eng, poses, None, k, opt, latent=L, shared=True)
+    explicit = _path(eng, poses, None, k, opt, latent=expanded, shared=False)
+    print(f"T {T} k {k} D {lay.dim}: {k * T * lay.dim} latent elements, cost {float(shared['cost'][0]):.6f}")
+    assert all(PH.same_bits(shared[n], explicit[n]) for n in OUTPUTS)
     assert not PH.same_bits(other["node"], shared["node"])
 
 

@@ -1,7 +1,8 @@
 """Swept collision checks along edges on the GPU (include/ikflow_amd_sweep.h; ikflow_amd/csrc/sweep_kernels.hip, sweep_math.h, api_sweep.hip, and the
 SWEEP form of k_path_lattice): ikf_sweep_edges against the fp64 reference of tests/sweep_helpers.py on guarded buffers, the lattice with a sweep
 against sequential numpy float32 on the engine's own node costs and verdicts (bit for bit), the purpose against fp64, the calls a sweep must not
-change, a blocked crossing, the flow in front, handle behaviour and the Python wrappers.
+change (also at more mask words than the sweep's grid has workgroups), a blocked crossing, the flow in front, handle behaviour and the Python
+wrappers.  sweep_helpers.CHAINS and the lattice cases run k_sweep_edges<ND> and k_path_lattice<ND, true> for every ND = 4 .. 8.
 
 Tolerance: world_helpers.BAND (1e-4) around a threshold, inside which a verdict is not compared; tests/test_sweep_math_host.py checks on the CPU
 that this leaves at most 5 % of the edges undecided and enough on either side."""
@@ -62,8 +63,8 @@ def _sweep(eng, a, b, S, reject_self=False, self_min=0.0, null=(), n=None, strea
 @pytest.mark.parametrize("scene,S", SH.EDGE_CASES)
 @pytest.mark.parametrize("which", SH.CHAINS)
 def test_sweep_edges_against_the_fp64_reference(which, scene, S):
-    """1, 63, 64, 65 and 257 edges (130 in the 64-obstacle scene: the cost of its fp64 reference) under the world rule alone, the self rule alone
-    and both: flags exact outside the band, the first blocked sample exact when no earlier sample is in the band."""
+    """Every chain size, 4 .. 8 joints: 1, 63, 64, 65 and 257 edges (130 in the 64-obstacle scene: the cost of its fp64 reference) under the world
+    rule alone, the self rule alone and both: flags exact outside the band, the first blocked sample exact when no earlier sample is in the band."""
     eng = _eng(which)
     c = SH.edge_case(which, scene, S)
     for rule in ("world", "self", "both"):
@@ -177,8 +178,16 @@ CASES = {
     "T3_k65": (3, 65, "panda", {}),
     "T65_k33": (65, 33, "panda", {}),
     "T5_k256": (5, 256, "panda", {}),
+    # kp = 128 with both slices full (k = 128, sweep_words = 2); kp = 256 with dead destinations and a last mask word of one live bit: the third
+    # of three at k = 129 (sweep_words = 3 of kPathMaskWords = 4), the fourth of four at k = 193; kp = 128 across a chunk of back-pointers
+    "T3_k128": (3, 128, "panda", {}),
+    "T3_k129": (3, 129, "panda", {}),
+    "T3_k193": (3, 193, "panda", {}),
+    "T66_k65": (CHUNK + 2, 65, "panda", {}),
     "2chunk+1": (2 * CHUNK + 1, 5, "panda", {}),
+    "ndof4": (65, 33, "syn4p", {}),     # k_path_lattice<4 .. 8, true>: a prismatic chain at 4 and 5 joints, a revolute one at 6
     "ndof5": (65, 33, "syn5p", {}),
+    "ndof6": (65, 33, "syn6r", {}),
     "ndof8": (65, 33, "fetch", {}),
     "q_start": (65, 33, "panda", dict(q_start=True)),
     "step_gate": (65, 33, "panda", dict(max_step=SH.STEP_GATE)),
@@ -287,6 +296,50 @@ def test_sweep_off_nothing_to_test_against_and_a_far_world_give_the_unswept_call
             self_only = _path(eng, L["poses"], L["q"], k, o, q_start)
             assert all(PH.same_bits(far[n], self_only[n]) for n in OUTPUTS)
             assert PH.same_bits(self_only["node"], plain["node"])
+
+
+# ---- 5b. more mask words than the sweep's grid has workgroups -----------------------------------------------------------------------------------------
+SWEEP_MAX_GRID = 2 ** 20   # kSweepMaxGrid of sweep_kernels.hip: beyond it a workgroup walks wave, wave + gridDim.x, ...
+
+
+def test_a_lattice_of_more_mask_words_than_the_sweep_grid_has_workgroups():
+    """T = 1025, k = 256: 1,049,600 mask words, 1,024 more than kSweepMaxGrid - those of the last waypoint's destinations are second trips of the
+    sweep kernel's strided loop.  (1) A sphere around the whole arm makes every node inadmissible: the "no path" outputs, and every mask word past
+    waypoint 0 is written as zero.  (2) The same handle and shape under a far world and S = 1: every edge is free, so every output equals the
+    unswept call's bit for bit (and that the numpy lattice); a word the sweep skipped is still zero and takes its destination's predecessors away."""
+    import time
+
+    from ikflow_amd.world import World
+    from test_path import _check_against_dp, _inputs
+
+    T, k = 1025, 256
+    assert T * k * ((k + 63) // 64) > SWEEP_MAX_GRID >= (T - 1) * k * ((k + 63) // 64)   # the smallest T that crosses the cap
+    orob = H.kin_robots("panda")[1]
+    eng = _eng("panda")
+    poses, q, _ = _inputs(orob, T, k, seed=T + k)
+    opt = _popt()
+    around = World()
+    around.add_sphere((0.0, 0.0, 0.3), 10.0)
+    eng.set_world(around, 0.0)
+    eng.set_path_sweep(1)
+    none = _path(eng, poses, q, k, opt)
+    assert np.isposinf(none["node"]).all()
+    assert np.isposinf(none["cost"][0]) and (none["index"] == -1).all() and (none["path"] == 0).all() and (none["reach"] == 0).all()
+    far = World()
+    far.add_sphere((50.0, 0.0, 0.0), 0.5)
+    eng.set_world(far, 1.0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    swept = _path(eng, poses, q, k, opt)
+    t1 = time.perf_counter()
+    eng.set_path_sweep(0)
+    unswept = _path(eng, poses, q, k, opt)
+    t2 = time.perf_counter()
+    print(f"T {T} k {k}: {T * k * 4} mask words, {k * k * (T - 1)} swept edges; the call with the sweep {t1 - t0:.3f} s, without {t2 - t1:.3f} s (guarded buffers included)")
+    assert np.isfinite(unswept["node"]).all() and np.isfinite(unswept["cost"][0])
+    for n in OUTPUTS:
+        assert PH.same_bits(swept[n], unswept[n]), f"{n}: the call under a sweep that blocks nothing differs from the unswept call, reachable_out tail {swept['reach'][-3:]}"
+    _check_against_dp(unswept, q, T, k, opt, what="T1025_k256")
 
 
 # ---- 6. a blocked crossing ---------------------------------------------------------------------------------------------------------------------------

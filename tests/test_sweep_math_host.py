@@ -49,10 +49,10 @@ def host_lib(tmp_path_factory):
 
 @pytest.mark.parametrize("which", SH.CHAINS)
 def test_sample_configurations_equal_sequential_numpy_float32_bit_for_bit(host_lib, which):
-    """(a) S in {1, 3, 16}, ndof 5, 7 and 8 (a prismatic joint among them): q_i = a + f32(i) / f32(S + 1) * (b - a), every operation rounded on its own."""
+    """(a) S in {1, 3, 16}, ndof 4 .. 8 (prismatic joints among them): q_i = a + f32(i) / f32(S + 1) * (b - a), every operation rounded on its own."""
     a, b = SH.edges(which)
     nd = a.shape[1]
-    assert nd == {"panda": 7, "fetch": 8, "syn5p": 5}[which]
+    assert nd == SH.NDOF[which] and sorted(set(SH.NDOF.values())) == [4, 5, 6, 7, 8]
     for S in (1, 3, 16):
         out = np.full((a.shape[0], S, nd), np.nan, np.float32)
         assert host_lib.sweep_host_samples(nd, a.ctypes.data, b.ctypes.data, a.shape[0], S, out.ctypes.data) == 0
@@ -106,8 +106,9 @@ def test_verdicts_against_the_fp64_reference_and_the_condition_the_gpu_tests_res
 
 
 def test_mask_geometry(host_lib):
-    """(d) k = 1, 63, 64, 65 and 256: words per destination, the word of an edge, the wave that produces it, the lanes that stand for a predecessor."""
-    for k in (1, 63, 64, 65, 256):
+    """(d) k = 1, 63, 64, 65, 128, 129, 193 and 256 (one to four words, the last one full or of a single live bit): words per destination, the word
+    of an edge, the wave that produces it, the lanes that stand for a predecessor."""
+    for k in (1, 63, 64, 65, 128, 129, 193, 256):
         words = host_lib.sweep_host_words(k)
         assert words == -(-k // 64)
         for T in (1, 2, 7):
