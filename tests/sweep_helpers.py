@@ -93,33 +93,59 @@ _EDGES = {}
 _CASES = {}
 
 
-def edges(which):
+def edges(which, seed=0):
     """257 edges of chain `which`: a inside the limits, b = a + U(-0.3, 0.3) per joint, both f32."""
-    if which not in _EDGES:
+    if (which, seed) not in _EDGES:
         orob = H.kin_robots(which)[1]
-        rng = np.random.default_rng(4100 + sum(map(ord, which)))
+        rng = np.random.default_rng(4100 + sum(map(ord, which)) + 1000 * seed)
         a = np.asarray(orob.sample_joint_angles(N_EDGES, 0.0, rng), np.float64)
         b = a + rng.uniform(-0.3, 0.3, a.shape)
-        _EDGES[which] = (np.ascontiguousarray(a, F), np.ascontiguousarray(b, F))
-    return _EDGES[which]
+        _EDGES[(which, seed)] = (np.ascontiguousarray(a, F), np.ascontiguousarray(b, F))
+    return _EDGES[(which, seed)]
 
 
-def edge_case(which, scene, S):
+N_EDGES_LARGE = 66     # with a capsule model of rank_helpers.capsule_models: one workgroup and two threads
+# Seeds of the edges of the 24-capsule cases: the first of 0 .. 9 under which, by the fp64 references alone, the share of surely blocked edges lies
+# strictly between 10 % and 90 % and at most 2 % of the edges are in the band, under the world rule and under both rules
+# (tests/test_sweep_math_host.py asserts it on the CPU).  A chain that is not listed takes seed 0.
+LARGE_SEEDS = {"syn4r": 1}
+
+
+def edge_case(which, scene, S, caps=None, seed=None):
     """-> dict: a, b [n x nd] f32, samples, world (the scene), world_cl / self_cl [n x S] fp64, world_thr - the median over the edges of the
-    minimum reference clearance over their samples -, self_thr - rank_helpers.clearance_threshold on the samples.  Computed once."""
-    key = (which, scene, S)
+    minimum reference clearance over their samples -, self_thr - rank_helpers.clearance_threshold on the samples.  Computed once.
+    caps: a name of rank_helpers.capsule_models (66 edges of seed LARGE_SEEDS, the scene built for that model; self_cl and self_thr are None until
+    with_self_rule fills them in: the oracle's self clearance of a large model costs as much as the rest), None: the small model."""
+    seed = (0 if caps is None else LARGE_SEEDS.get(which, 0)) if seed is None else seed
+    key = (which, scene, S, caps, seed)
     if key not in _CASES:
-        robot, orob = H.kin_robots(which)
-        caps = RH.collision_capsules(robot)
-        a, b = edges(which)
-        n = N_EDGES_FULL64 if scene == "full64" else N_EDGES
+        orob = H.kin_robots(which)[1]
+        model = RH.capsules(which, caps)
+        a, b = edges(which, seed)
+        n = N_EDGES_LARGE if caps is not None else N_EDGES_FULL64 if scene == "full64" else N_EDGES
         a, b = a[:n], b[:n]
-        world = WH.scene(which, scene)
+        world = WH.scene(which, scene, caps)
         smp = samples_f32(a, b, S)
-        wc, sc = sample_clearances(orob, caps, world, smp)
-        _CASES[key] = dict(a=a, b=b, samples=smp, world=world, world_cl=wc, self_cl=sc, world_thr=float(np.median(wc.min(1))),
-                           self_thr=RH.clearance_threshold(orob, caps, torch.tensor(smp.reshape(-1, a.shape[1]))))
+        wc, sc = sample_clearances(orob, model, world, smp, want_self=caps is None)
+        _CASES[key] = dict(a=a, b=b, samples=smp, world=world, world_cl=wc, self_cl=sc, world_thr=float(np.median(wc.min(1))), which=which, caps=caps,
+                           self_thr=None if sc is None else RH.clearance_threshold(orob, model, torch.tensor(smp.reshape(-1, a.shape[1]))))
     return _CASES[key]
+
+
+def with_self_rule(c):
+    """The self clearances and their median of an edge_case of a large capsule model, computed once, on demand."""
+    if c["self_cl"] is None:
+        orob = H.kin_robots(c["which"])[1]
+        n, S, nd = c["samples"].shape
+        c["self_cl"] = RH.clearance(orob, RH.capsules(c["which"], c["caps"]), torch.tensor(c["samples"].reshape(n * S, nd))).reshape(n, S)
+        c["self_thr"] = float(np.median(c["self_cl"]))
+    return c
+
+
+def shares_hold(v):
+    """The condition of the 24-capsule cases on verdicts(...): blocked share strictly between 10 % and 90 %, at most 2 % of the edges in the band."""
+    band, blocked, free = shares(v)
+    return band <= 0.02 and 0.1 < blocked < 0.9
 
 
 def case_verdicts(c, rule, n=None):
@@ -231,17 +257,17 @@ LATTICE_QUANTILE = 0.25
 _LATTICES = {}
 
 
-def lattice_inputs(which, T, k, seed):
+def lattice_inputs(which, T, k, seed, caps=None):
     """-> dict: poses [T x 7], q [k * T x nd] tile-major, q_start (the truth of waypoint 0 plus 0.05 rad), world, world_cl / self_cl [k * T] fp64,
-    world_thr, self_thr.  Computed once."""
-    key = (which, T, k, seed)
+    world_thr, self_thr.  Computed once.  caps: a name of rank_helpers.capsule_models (and the scene built for it), None: the small model."""
+    key = (which, T, k, seed, caps)
     if key not in _LATTICES:
-        robot, orob = H.kin_robots(which)
-        caps = RH.collision_capsules(robot)
+        orob = H.kin_robots(which)[1]
+        caps = RH.capsules(which, caps)
         poses, q, q_true = path_inputs(orob, T, k, seed)
-        world = WH.scene(which, LATTICE_SCENE)
+        world = WH.scene(which, LATTICE_SCENE, key[4])
         wc = WH.reference(orob, caps, world, q)["clearance"]
-        sc = ko.capsule_clearance(orob, caps, (), q.double()).numpy()
+        sc = RH.clearance(orob, caps, q)
         # ... but never so high that a waypoint is left without an admissible candidate (few candidates, all close to one colliding truth)
         thr = lambda c: float(min(np.quantile(c, LATTICE_QUANTILE), c.reshape(k, T).max(0).min() - 1e-3))
         _LATTICES[key] = dict(poses=poses, q=q, q_start=(q_true[0] + 0.05).contiguous(), world=world, world_cl=wc, self_cl=sc,
@@ -256,6 +282,10 @@ def lattice_inputs(which, T, k, seed):
 LATTICE_SEEDS = {("panda", 1, 1): 1, ("panda", 1, 5): 2, ("panda", 2, 3): 3, ("panda", 9, 1): 0, ("panda", 7, 64): 0, ("panda", 3, 65): 0,
                  ("panda", 65, 33): 1, ("panda", 5, 256): 0, ("syn5p", 65, 33): 1, ("fetch", 65, 33): 9,
                  ("syn4p", 65, 33): 1, ("syn6r", 65, 33): 7, ("panda", 3, 128): 0, ("panda", 3, 129): 0, ("panda", 3, 193): 0, ("panda", 66, 65): 0}
+# the swept lattice of the 24-capsule model (chain, T, k, samples per edge): the seed is the first of 0 .. 9 for which, by the references and the
+# host build on the CPU (tests/test_sweep_math_host.py), a swept path exists and the edges between admissible nodes hold blocked and free ones
+LARGE_LATTICE = ("panda", 6, 8, 2)
+LARGE_LATTICE_SEED = 1
 SELF_RULE_SEED = 3      # (65, 33) with the self rule on top of the world: under seed 1 no swept path is left
 STEP_GATE = 0.8         # (65, 33) with a step gate: under 0.5 rad no swept path is left
 

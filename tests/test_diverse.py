@@ -16,7 +16,7 @@ import diverse_helpers as DH
 import helpers as H
 import rank_helpers as RH
 from ikflow_amd import _lib
-from test_ranked import DEV, GUARD, _check_window, _eng, _opt as _rank_opt, _rank, _solver, _window
+from test_ranked import DEV, GUARD, _check_window, _eng, _eng_with, _opt as _rank_opt, _rank, _small_model_back, _solver, _window  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 OUTPUTS = ("q_out", "score", "index", "sep", "kept", "count", "row_score")
@@ -71,7 +71,8 @@ def _check_against_numpy(out, q, m, k, opt, w=None, what=""):
 
 
 # ---- 1. the selection against sequential numpy float32, on every shape at which the kernel takes another path -------------------------------------
-SHAPES = [(1, 1), (1, 2), (2, 63), (1, 64), (3, 65), (65, 16), (1, 255), (2, 256), (1, 257), (2, 1024)]
+# (k = 512 and 513: k_diverse_select goes from 128 to 256 threads between them)
+SHAPES = [(1, 1), (1, 2), (2, 63), (1, 64), (3, 65), (65, 16), (1, 255), (2, 256), (1, 257), (2, 1024), (1, 512), (1, 513)]
 ROBOTS = ("panda", "fetch", "fetch_arm", "syn4r", "syn5p", "syn6r", "syn7p", "syn8r")
 VARIANTS = ("thresholds", "limits_wild", "collisions", "weights", "early_stop")
 
@@ -354,3 +355,64 @@ def test_generate_diverse_ik_solutions_end_to_end():
     none = s.generate_diverse_ik_solutions(y, k, nk, latent=L, pos_error_threshold=0.0)
     assert (none.n_kept == 0).all() and (none.n_admissible == 0).all() and (none.repeat_index == -1).all() and (none.solutions == 0).all()
     assert torch.isposinf(none.scores).all() and torch.isposinf(none.separation).all()
+
+
+# ---- 9. the 24-capsule model, and ties of a farthest-point round across lanes and waves -----------------------------------------------------------
+def test_row_scores_with_24_capsules_are_the_rankings(_small_model_back):
+    """The score stage under the 24-capsule model (k_rank_candidates with 74240 B of capsule slices): row scores, counts and slot 0 bit-equal to
+    ikf_rank_candidates' on the same rows, the selection the numpy selection on them.  min_clearance: the median of the fp64 clearances."""
+    which = "panda"
+    c = RH.capsule_case(which, "caps24", "tile64")
+    m, k = c["m"], c["k"]
+    eng = _eng_with(which, "caps24", _small_model_back)
+    opt = _dopt(4, collisions=True, min_clearance=c["min_clearance"], min_sep=0.05)
+    out = _div(eng, c["poses"], c["q"], k, opt)
+    r = _rank(eng, c["poses"], c["q"], k, _rank_opt(1, collisions=True, min_clearance=c["min_clearance"]))
+    assert DH.same_bits(out["row_score"], r["row_score"]) and np.array_equal(out["count"], r["count"])
+    assert DH.same_bits(out["index"][:, :1], r["index"]) and DH.same_bits(out["score"][:, :1], r["score"]) and DH.same_bits(out["q_out"][:, :1], r["q_out"])
+    sure = np.abs(c["clearance"] - c["min_clearance"]) > 1e-4
+    assert np.array_equal(np.isposinf(out["row_score"])[sure], (c["clearance"] < c["min_clearance"])[sure]) and 0.1 < np.isposinf(out["row_score"]).mean() < 0.9
+    _check_against_numpy(out, c["q"], m, k, opt, what="caps24")
+
+
+def _tie_case(k, seed):
+    """One pose, k candidates on a grid of 2^-8 rad, so that every difference, square and sum of a dist2 is exact in float32.  Row P is the
+    configuration whose pose is asked for (the lowest score: slot 0).  Fourteen rows are P +- 0.25 rad along each of the Panda's seven joints:
+    pairs mirrored about P.  After any picks among them every one of those still alive has near2 = 0.0625 exactly - its distance to P; to a
+    picked row it is 0.125 or 0.25 - so every round is a tie among all of them, and the lowest index must win.  The other rows lie within
+    0.0625 rad per joint of P and are never the farthest.  -> (poses, q tile-major, P, the tied indices ascending)."""
+    orob = H.kin_robots("panda")[1]
+    rng = np.random.default_rng(seed)
+    lo, hi = RH.limits(orob)
+    mid = (0.5 * (lo + hi)).numpy().astype(np.float64)
+    qp = np.round(mid * 256.0) / 256.0
+    q = qp[None, :] + rng.integers(-16, 17, (k, 7)) / 256.0
+    tied = np.sort(rng.choice(np.arange(1, k), 14, replace=False))
+    P = 0
+    for i, r in enumerate(rng.permutation(tied)):
+        q[r] = qp + (0.25 if i % 2 == 0 else -0.25) * np.eye(7)[i // 2]
+    q[P] = qp
+    assert (q > lo.numpy() + 0.01).all() and (q < hi.numpy() - 0.01).all() and (q.astype(np.float32) == q).all()
+    from oracle import kinematics_oracle as ko
+
+    poses = ko.forward_kinematics(orob, torch.tensor(qp[None])).float().contiguous()
+    return poses, torch.tensor(q, dtype=torch.float32).contiguous(), P, tied
+
+
+@pytest.mark.parametrize("k", [200, 300, 1000])
+def test_a_tie_of_a_farthest_point_round_goes_to_the_lower_index_in_whatever_lane_or_wave(k):
+    """k = 200: one wave, the tied rows in different lanes (__shfl_xor steps of diverse_merge); k = 300: two waves; k = 1000: four waves, up to
+    four candidates per thread.  Candidate r sits in thread r mod B, wave (r mod B) / 64: among the tied rows a lower index sits in a higher
+    wave (or lane) than a higher index and the other way round, so neither the order of the lanes nor of the waves gives the right row by
+    itself.  Every output bit for bit against DH.select_poses; the picks are the tied indices in ascending order."""
+    eng = _eng("panda")
+    poses, q, P, tied = _tie_case(k, seed=k)
+    B = 64 if k <= 256 else 128 if k <= 512 else 256
+    place = (tied % B) // 64 if B > 64 else tied % 64   # wave, or lane within the one wave
+    assert len(set(place.tolist())) >= 2 and (np.diff(place) < 0).any() and (np.diff(place) > 0).any()
+    n_keep = 12
+    opt = _dopt(n_keep)
+    out = _div(eng, poses, q, k, opt)
+    _check_against_numpy(out, q, 1, k, opt, what=f"tie k {k}")
+    assert out["index"][0].tolist() == [P] + tied[:n_keep - 1].tolist(), (out["index"][0], tied)
+    assert (out["sep"][0, 1:] == np.float32(0.25)).all() and out["kept"][0] == n_keep and out["count"][0] == k

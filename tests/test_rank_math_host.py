@@ -34,16 +34,20 @@ def host_lib(tmp_path_factory):
     return lib
 
 
-def _set_collision(lib, robot):
-    robot.set_collision_capsules(RH.collision_capsules(robot))
+def _set_collision(lib, robot, caps=None, every_pair=False):
+    """caps: a capsule list (None: the small model); every_pair: all n (n - 1) / 2 pairs instead of the generated ones."""
+    robot.set_collision_capsules(RH.collision_capsules(robot) if caps is None else caps)
     folded, pairs = robot._collision_model
-    arr = (_lib.ikf_capsule * len(folded))()
+    if every_pair:
+        pairs = RH.all_pairs(len(folded))
+    arr = (_lib.ikf_capsule * max(len(folded), 1))()
     for c, (frame, p0, p1, r) in zip(arr, folded):
         c.frame, c.radius = int(frame), float(r)
         for i in range(3):
             c.p0[i], c.p1[i] = float(p0[i]), float(p1[i])
-    flat = (C.c_int32 * (2 * len(pairs)))(*[int(v) for ab in pairs for v in ab])
+    flat = (C.c_int32 * max(2 * len(pairs), 1))(*[int(v) for ab in pairs for v in ab])
     lib.rank_host_set_collision(arr, len(folded), flat, len(pairs))
+    robot.set_collision_capsules(RH.collision_capsules(robot))   # (the robots are shared: the small model is back)
 
 
 def _scores(lib, chain, opt, poses, q, q_ref, k, clearance=False):
@@ -186,3 +190,79 @@ def test_chunk_rule_is_sane_on_every_shape(host_lib):
         assert host_lib.rank_host_chunks(1, 5000, n_cu) > 1 and host_lib.rank_host_chunks(3, 1000, n_cu) > 1
         assert host_lib.rank_host_chunks(1000, 2, n_cu) == 1 and host_lib.rank_host_chunks(1, 1, n_cu) == 1
     assert [host_lib.rank_host_tile_poses(m) for m in (1, 2, 3, 33, 64, 65, 10 ** 6)] == [1, 2, 4, 64, 64, 64, 64]
+
+
+# ---- the capsule models by size (rank_helpers.capsule_models) -----------------------------------------------------------------------------------
+TRUNCATION_CHAINS = ("syn4r", "panda", "fetch", "syn6r")   # every chain that meets its 24-capsule model in a GPU test
+
+
+def test_the_capsule_models_have_the_counts_and_occupy_every_frame():
+    for which in H.KIN_ALL:
+        robot = H.kin_robots(which)[0]
+        models = RH.capsule_models(robot)
+        assert [len(models[f"caps{n}"]) for n in RH.CAPSULE_COUNTS] == list(RH.CAPSULE_COUNTS) and models["caps5"] == RH.collision_capsules(robot)
+        for n in RH.LARGE_COUNTS:
+            robot.set_collision_capsules(models[f"caps{n}"])
+            folded, pairs = robot._collision_model
+            per_frame = np.bincount([f[0] for f in folded], minlength=robot.ndof + 1)
+            assert len(per_frame) == robot.ndof + 1 and (per_frame >= 1).all() and per_frame.max() >= 2, (which, n, per_frame)
+            assert len(pairs) > 9 and len(pairs) == n * (n - 1) // 2 - sum(c * (c - 1) // 2 for c in per_frame)
+        robot.set_collision_capsules(models["caps5"])
+
+
+@pytest.mark.parametrize("which", TRUNCATION_CHAINS)
+def test_the_later_capsules_of_the_24_capsule_model_decide_rows(which):
+    """From the fp64 oracle alone, on the rows of the tile64 case: the clearance under the first 16 capsules, and under the first 5, differs from
+    the clearance under all 24 on at least a tenth of the rows - so a loop that stops early, or a slice stride that leaves the later capsules
+    out, changes results."""
+    orob = H.kin_robots(which)[1]
+    c = RH.capsule_case(which, "caps24", "tile64")
+    caps = RH.capsules(which, "caps24")
+    full = c["clearance"]
+    shares = [float((RH.clearance(orob, caps[:n], c["q"]) != full).mean()) for n in (16, 5)]
+    print(f"{which}: the clearance changes on {shares[0]:.3f} of the rows without capsules 17 .. 24, on {shares[1]:.3f} without 6 .. 24; "
+          f"fp64 clearances {full.min():.4f} .. {full.max():.4f}")
+    assert min(shares) >= 0.1, (which, shares)
+
+
+HOST_CASES = [(w, mo) for w in RH.CASE_CHAINS for mo in RH.REJECTING]
+
+
+@pytest.mark.parametrize("which,model", HOST_CASES)
+def test_row_scores_of_the_kernel_source_with_every_capsule_count(host_lib, which, model):
+    """The capsule cases of tests/test_ranked.py through the kernel source on the CPU: clearance within 2e-5 of the oracle, row scores by
+    check_row_scores.  And the condition those tests rest on, from the oracle alone: with min_clearance the median of the rows' clearances
+    (seed: rank_helpers.CASE_SEEDS) the inadmissible share lies strictly between 10 % and 90 % and at most 2 % of the rows lie inside a band."""
+    robot, orob = H.kin_robots(which)
+    chain = _chain_bytes(robot, host_lib)
+    caps = RH.capsules(which, model)
+    _set_collision(host_lib, robot, caps)
+    shapes = ["tile1", "tile64"] + (["chunked"] if model == "caps14" or (which, model) == ("panda", "caps24") else [])
+    for shape in shapes:
+        c = RH.capsule_case(which, model, shape)
+        opt = _opt(collisions=True, min_clearance=c["min_clearance"])
+        got, cl = _scores(host_lib, chain, opt, c["poses"], c["q"], None, c["k"], clearance=True)
+        assert np.abs(cl - c["clearance"]).max() <= 2e-5, (which, model, shape, float(np.abs(cl - c["clearance"]).max()))
+        ref = RH.reference(orob, c["poses"], c["q"], c["k"], 0.01, caps=caps, min_clearance=c["min_clearance"], self_clearance=c["clearance"])
+        near, bad = RH.shares(ref)
+        worst = RH.check_row_scores(got, ref, f"{which} {model} {shape}")
+        print(f"host {which} {model} {shape}: seed {RH.CASE_SEEDS.get((which, model, shape), 0)}, near-band share {near:.4f}, inadmissible share {bad:.4f}, "
+              f"worst {worst:.3f} of eps")
+        assert RH.shares_hold(ref), (which, model, shape, near, bad)
+
+
+@pytest.mark.parametrize("which", RH.CASE_CHAINS)
+def test_models_without_pairs_and_with_every_pair_on_the_host(host_lib, which):
+    """caps0 and caps1 have no pair: the clearance is 3.0e38 and reject_collisions changes no score.  caps24 with all 276 pairs listed: the
+    oracle, which skips same-frame pairs, bounds the clearance from above."""
+    robot, orob = H.kin_robots(which)
+    chain = _chain_bytes(robot, host_lib)
+    c = RH.capsule_case(which, "caps24", "tile64")
+    for model in ("caps0", "caps1"):
+        _set_collision(host_lib, robot, RH.capsules(which, model))
+        plain = _scores(host_lib, chain, _opt(), c["poses"], c["q"], None, c["k"])
+        got, cl = _scores(host_lib, chain, _opt(collisions=True, min_clearance=0.05), c["poses"], c["q"], None, c["k"], clearance=True)
+        assert H.same_bits(got, plain) and (cl == np.float32(3.0e38)).all(), (which, model)
+    _set_collision(host_lib, robot, RH.capsules(which, "caps24"), every_pair=True)
+    _, cl = _scores(host_lib, chain, _opt(), c["poses"], c["q"], None, c["k"], clearance=True)
+    assert (cl <= c["clearance"] + 2e-5).all() and (cl < c["clearance"] - 1e-4).any()   # (and same-frame pairs do decide rows)

@@ -519,3 +519,206 @@ def test_candidate_buffers_regrow_across_families_and_are_released_with_the_hand
     torch.cuda.synchronize()
     free1, stat1 = torch.cuda.mem_get_info(DEV)[0], torch.cuda.memory_reserved(DEV)
     assert free0 - free1 <= stat1 - stat0, f"{free0 - free1 - (stat1 - stat0)} bytes of device memory did not come back with the handle"
+
+
+# ---- 8. every capsule count: the LDS slices of k_rank_candidates on both sides of its 48 KiB opt-in --------------------------------------------
+@pytest.fixture
+def _small_model_back():
+    """The engines are shared with the other test modules: after a test that set another capsule model, the small one is back."""
+    used = []
+    yield used
+    for which in used:
+        _eng(which, collisions=True)
+
+
+def _eng_with(which, model, used, every_pair=False):
+    """The shared engine of the chain with capsule model `model` of rank_helpers.capsule_models; every_pair: with all n (n - 1) / 2 pairs listed,
+    same-frame ones included, instead of the pairs Robot.set_collision_capsules generates."""
+    from ikflow_amd.engine import kinematics_engine_for
+
+    robot = H.kin_robots(which)[0]
+    eng = kinematics_engine_for(robot, DEV)
+    robot.set_collision_capsules(RH.capsules(which, model))
+    folded, pairs = robot._collision_model
+    eng.set_collision_model(folded, RH.all_pairs(len(folded)) if every_pair else pairs)
+    eng._collision_source = None if every_pair else robot._collision_model
+    used.append(which)
+    return eng
+
+
+def _check_the_straddle(model, m, n_keep, lds, world=False):
+    """The call of the count below a crossing of the opt-in line stays at or under 49152 B, the call of the count above exceeds it."""
+    for below, above, tile, keep, w in RH.CROSSINGS:
+        if (tile, keep, w) == (RH.tile_poses(m), RH.keep_capacity(n_keep), world):
+            if model == below:
+                assert lds <= RH.LDS_OPT_IN, (model, lds)
+            if model == above:
+                assert lds > RH.LDS_OPT_IN, (model, lds)
+
+
+def test_the_crossings_of_the_opt_in_line_are_where_the_models_stand():
+    """From the formula of rank_kernels.hip alone: each crossing named in rank_helpers.CROSSINGS lies between two models of CAPSULE_COUNTS that are
+    one capsule apart, the shapes of the capsule cases have the tile and capacity of a crossing, and 24 capsules give the documented maxima."""
+    for below, above, tile, keep, world in RH.CROSSINGS:
+        nb, na = int(below[4:]), int(above[4:])
+        assert na == nb + 1 and nb in RH.CAPSULE_COUNTS and na in RH.CAPSULE_COUNTS
+        m = 1 if tile == 1 else 33
+        assert RH.tile_poses(m) == tile
+        assert RH.rank_lds_bytes(m, keep, nb, world) <= RH.LDS_OPT_IN < RH.rank_lds_bytes(m, keep, na, world)
+    for shape in ("tile1", "tile64", "chunked"):
+        m, k, n_keep = RH.CASE_SHAPES[shape]
+        assert (RH.tile_poses(m), RH.keep_capacity(n_keep)) == ((1, 1) if shape == "tile1" else (64, 16)) and n_keep <= k
+    assert RH.rank_lds_bytes(64, 16, 24) == 82688 and RH.rank_lds_bytes(64, 16, 24, world=True) == 86784
+    assert RH.rank_lds_bytes(64, 16, 5) < RH.LDS_OPT_IN // 2   # (the small model of every earlier test is nowhere near the line)
+
+
+CAPSULE_CASES = [(w, mo, sh) for w in RH.CASE_CHAINS for mo in RH.REJECTING for sh in ("tile1", "tile64")] + \
+                [(w, "caps14", "chunked") for w in RH.CASE_CHAINS] + [("panda", "caps24", "chunked")]
+
+
+@pytest.mark.parametrize("which,model,shape", CAPSULE_CASES)
+def test_row_scores_and_selection_with_every_capsule_count(which, model, shape, _small_model_back):
+    """reject_collisions with 5, 11 .. 16 and 24 capsules on chains of 4, 7 and 8 joints, min_clearance the median of the fp64 clearances: row
+    scores by check_row_scores, the selection bit for bit.  tile1: tile 1, capacity 1; tile64: tile 64, capacity 16; chunked: two chunks, keep 16
+    (with 14 capsules, and on the Panda with 24: the documented maximum of 82688 B).  The LDS bytes of the call come from the kernel's formula:
+    the count below a crossing stays under the opt-in line, the count above is over it."""
+    orob = H.kin_robots(which)[1]
+    c = RH.capsule_case(which, model, shape)
+    m, k, n_keep = c["m"], c["k"], c["n_keep"]
+    caps = RH.capsules(which, model)
+    eng = _eng_with(which, model, _small_model_back)
+    lds = RH.rank_lds_bytes(m, n_keep, len(caps))
+    _check_the_straddle(model, m, n_keep, lds)
+    assert eng.rank_chunks(m, k) == (2 if shape == "chunked" else 1)
+    if model == "caps24" and shape != "tile1":
+        assert lds == 82688
+    ref = RH.reference(orob, c["poses"], c["q"], k, 0.01, caps=caps, min_clearance=c["min_clearance"], self_clearance=c["clearance"])
+    assert RH.shares_hold(ref), RH.shares(ref)
+    out = _rank(eng, c["poses"], c["q"], k, _opt(n_keep=n_keep, collisions=True, min_clearance=c["min_clearance"]))
+    worst = RH.check_row_scores(out["row_score"], ref, f"{which} {model} {shape}")
+    print(f"{which} {model} {shape}: {lds} B of LDS, worst {worst:.3f} of eps, shares (near, inadmissible) {RH.shares(ref)}")
+    _check_selection(out, c["q"], m, k, n_keep, f"{which} {model} {shape}")
+
+
+@pytest.mark.parametrize("which", RH.CASE_CHAINS)
+def test_every_pair_of_24_capsules_rejects_at_least_what_the_generated_pairs_reject(which, _small_model_back):
+    """All 276 pairs listed, same-frame ones included (the longest pair loop).  The oracle skips same-frame pairs, so its clearance is an upper
+    bound: every row it surely rejects is rejected, no row is admitted that the generated pairs reject, and a row that is admitted keeps its
+    score.  (The clearance of a same-frame pair does not depend on q; where such a pair lies under the threshold every row is rejected.)  With a
+    threshold no pair can reach - the radii are 15 mm at most - the long loop rejects nothing and every output has the bits of the short one's."""
+    c = RH.capsule_case(which, "caps24", "tile64")
+    m, k, n_keep = c["m"], c["k"], c["n_keep"]
+    for thr in (c["min_clearance"], -1.0):
+        opt = _opt(n_keep=n_keep, collisions=True, min_clearance=thr)
+        generated = _rank(_eng_with(which, "caps24", _small_model_back), c["poses"], c["q"], k, opt)
+        every = _rank(_eng_with(which, "caps24", _small_model_back, every_pair=True), c["poses"], c["q"], k, opt)
+        surely_rejected = c["clearance"] < thr - 1e-4
+        assert np.isposinf(every["row_score"][surely_rejected]).all() and surely_rejected.any() == (thr > -1.0)
+        assert (np.isposinf(every["row_score"]) | ~np.isposinf(generated["row_score"])).all()   # (more pairs never admit a row)
+        both = np.isfinite(every["row_score"])
+        assert H.same_bits(every["row_score"][both], generated["row_score"][both])
+        _check_selection(every, c["q"], m, k, n_keep, f"{which} every pair")
+    assert both.all() and all(H.same_bits(every[n], generated[n]) for n in OUTPUTS)
+
+
+@pytest.mark.parametrize("model", ["caps0", "caps1"])
+@pytest.mark.parametrize("which", RH.CASE_CHAINS)
+def test_a_model_without_pairs_rejects_nothing(which, model, _small_model_back):
+    """No capsule (a slice of one float per thread) and one capsule (no pair): with reject_collisions the kernel takes the collision branch, and
+    every output has the bits of the same call without the rule - on every shape of the capsule cases, with limits rejected so that lists differ."""
+    orob = H.kin_robots(which)[1]
+    eng = _eng_with(which, model, _small_model_back)
+    for shape, (m, k, n_keep) in RH.CASE_SHAPES.items():
+        poses, q, q_ref = RH.candidates(orob, m, k, seed=3, wild=True)
+        without = _rank(eng, poses, q, k, _opt(n_keep=n_keep, limits=True, ref_weight=0.05), q_ref)
+        with_rule = _rank(eng, poses, q, k, _opt(n_keep=n_keep, limits=True, ref_weight=0.05, collisions=True, min_clearance=0.05), q_ref)
+        assert all(H.same_bits(with_rule[n], without[n]) for n in OUTPUTS), (which, model, shape)
+        assert 0 < np.isposinf(without["row_score"]).sum() < k * m
+        _check_selection(with_rule, q, m, k, n_keep, f"{which} {model} {shape}")
+
+
+# ---- 9. the tile widths, keep counts and chains the selection had not met ---------------------------------------------------------------------
+# (m, k): every pose count of 2, 9, 16, 17, 32 and 33 with a k that runs in one chunk and a k that runs in several
+WIDTH_SHAPES = [(2, 40), (2, 1009), (9, 12), (9, 200), (16, 20), (16, 150), (17, 12), (17, 100), (32, 12), (32, 70), (33, 7), (33, 40)]
+
+
+def test_the_width_shapes_hold_every_width_with_one_chunk_and_with_several():
+    eng = _eng("panda")
+    seen = {(RH.tile_poses(m), eng.rank_chunks(m, k) > 1) for m, k in WIDTH_SHAPES}
+    print("tile width and chunks per (m, k):", {s: (RH.tile_poses(s[0]), eng.rank_chunks(*s)) for s in WIDTH_SHAPES})
+    for width in (2, 16, 32, 64):
+        assert (width, False) in seen and (width, True) in seen, (width, seen)
+    for m in (2, 9, 16, 17, 32, 33):
+        chunked = {eng.rank_chunks(mm, k) > 1 for mm, k in WIDTH_SHAPES if mm == m}
+        assert chunked == {False, True}, (m, chunked)
+    assert [RH.tile_poses(m) for m in (1, 2, 3, 9, 16, 17, 32, 33, 64, 65)] == [1, 2, 4, 16, 16, 32, 32, 64, 64, 64]
+
+
+@pytest.mark.parametrize("m,k", WIDTH_SHAPES)
+def test_selection_at_the_widths_2_16_and_32(m, k):
+    """The check of test_selection_equals_the_lexsort_of_the_engines_row_scores at the widths whose __shfl_xor steps and wave hand-over had not
+    run, for every capacity and for keep counts strictly inside one (2, 3, 5, 15)."""
+    orob = H.kin_robots("panda")[1]
+    eng = _eng("panda")
+    poses, q, _ = RH.candidates(orob, m, k, seed=m + k)
+    for n_keep in sorted({min(n, k) for n in (1, 2, 3, 4, 5, 15, 16)}):
+        out = _rank(eng, poses, q, k, _opt(n_keep=n_keep, max_pos=0.03, limits=True))
+        _check_selection(out, q, m, k, n_keep, f"m {m} k {k} n_keep {n_keep}")
+    if k >= 40:
+        assert (out["count"] < k).any() and (out["count"] > 0).any()
+
+
+@pytest.mark.parametrize("m,k", [(2, 1009), (3, 1009), (64, 65), (257, 50)])
+def test_keep_counts_inside_a_capacity_class_on_chunked_shapes(m, k):
+    """n_keep 2, 3, 5 and 15: the partial lists of a chunk have stride n_keep while the register list holds 4 or 16 entries.  k = 1009 is prime,
+    so the last chunk is shorter than the others."""
+    orob = H.kin_robots("panda")[1]
+    eng = _eng("panda")
+    chunks = eng.rank_chunks(m, k)
+    assert chunks > 1 and (k != 1009 or k % -(-k // chunks) != 0)
+    poses, q, _ = RH.candidates(orob, m, k, seed=m + k)
+    for n_keep in (2, 3, 5, 15):
+        out = _rank(eng, poses, q, k, _opt(n_keep=n_keep, max_pos=0.03, limits=True))
+        _check_selection(out, q, m, k, n_keep, f"m {m} k {k} n_keep {n_keep}")
+    assert (out["count"] < k).any() and (out["count"] > 0).any()
+
+
+@pytest.mark.parametrize("which", ["syn4p", "syn5r", "syn6p", "syn8r"])
+def test_chunked_selection_on_chains_of_4_5_6_and_8_joints(which):
+    """Exact selection over several chunks, without capsules, on the chain sizes that had met it only with keep counts 1, 4 and 16."""
+    orob = H.kin_robots(which)[1]
+    eng = _eng(which)
+    for m, k in ((3, 1009), (65, 64)):
+        assert eng.rank_chunks(m, k) > 1
+        poses, q, _ = RH.candidates(orob, m, k, seed=m + k)
+        for n_keep in (1, 3, 4, 15, 16):
+            out = _rank(eng, poses, q, k, _opt(n_keep=n_keep, max_pos=0.03, limits=True))
+            _check_selection(out, q, m, k, n_keep, f"{which} m {m} k {k} n_keep {n_keep}")
+        assert (out["count"] < k).any() and (out["count"] > 0).any()
+
+
+# (m, k, n_keep): one chunk each; the second wave of the workgroup holds at least n_keep of the k repeats of a pose
+SECOND_WAVE_SHAPES = [(1, 200, 16), (2, 100, 16), (3, 80, 16), (5, 100, 16), (9, 40, 16), (16, 60, 15), (17, 12, 4), (33, 12, 4), (64, 9, 4), (1, 130, 1)]
+
+
+@pytest.mark.parametrize("m,k,n_keep", SECOND_WAVE_SHAPES)
+def test_a_list_whose_every_entry_comes_from_the_second_wave(m, k, n_keep):
+    """The n_keep best candidates of every pose are 1 mm-scale perturbations of the truth placed at repeats that threads of the second wave own
+    (repeat r belongs to slice r mod S, S = 128 / tile_poses; the slices S / 2 .. S - 1 are the second wave's); all the others are 0.3 rad off.
+    Then every entry of the result, the last one of a full register list included, has crossed the LDS hand-over between the waves."""
+    orob = H.kin_robots("panda")[1]
+    eng = _eng("panda")
+    assert eng.rank_chunks(m, k) == 1
+    S = 128 // RH.tile_poses(m)
+    second = [r for r in range(k) if r % S >= S // 2][:n_keep]
+    assert len(second) == n_keep
+    g = torch.Generator().manual_seed(m + k)
+    q_true, poses = H.reachable_poses(orob, m, 70 + m)
+    scale = torch.full((k,), 0.3)
+    scale[second] = 1e-3 * (1.0 + torch.rand(n_keep, generator=g))
+    from oracle import kinematics_oracle as ko
+
+    q = ko.clamp_to_joint_limits(orob, (q_true[None] + torch.randn(k, m, orob.ndof, generator=g) * scale[:, None, None]).reshape(k * m, -1)).float().contiguous()
+    out = _rank(eng, poses.float().contiguous(), q, k, _opt(n_keep=n_keep))
+    _check_selection(out, q, m, k, n_keep, f"m {m} k {k} n_keep {n_keep}")
+    assert (np.sort(out["index"], axis=1) == np.array(second)).all(), "the best candidates are not the ones placed in the second wave"

@@ -18,9 +18,9 @@ import rank_helpers as RH
 import sweep_helpers as SH
 import world_helpers as WH
 from ikflow_amd import _lib
-from test_path import CHUNK, OUTPUTS, _path, _popt
-from test_ranked import DEV, GUARD, INT_SENTINEL
-from test_world import _USED, _eng
+from test_path import CHUNK, OUTPUTS, _check_nodes_are_rank_scores, _path, _popt
+from test_ranked import DEV, GUARD, INT_SENTINEL, _small_model_back  # noqa: F401  (a fixture)
+from test_world import _USED, _eng, _eng_model
 
 pytestmark = pytest.mark.gpu
 BYTE_SENTINEL = 0xAB
@@ -512,3 +512,50 @@ def test_python_wrappers():
         assert not bool(s.path_collides(b.path, S).any()) and float(b.cost) >= float(a.cost)
     s.set_path_sweep(0)
     s.set_world(None)
+
+
+# ---- 11. the 24-capsule model: the LDS slices of k_sweep_edges at their maximum, and a swept lattice ------------------------------------------------
+LARGE_CHAINS = ("syn4r", "syn6r", "fetch")   # 4, 6 and 8 joints
+
+
+@pytest.mark.parametrize("rule", ["world", "both"])
+@pytest.mark.parametrize("which", LARGE_CHAINS)
+def test_sweep_edges_with_24_capsules_in_the_64_obstacle_scene(which, rule, _small_model_back):
+    """k_sweep_edges with 24 capsules and 64 obstacles - 41216 B of dynamic LDS, its maximum - on 1, 63, 64, 65 and 66 edges: flags exact outside
+    the band, the first blocked sample exact when no earlier sample is in the band, under the world rule and under both rules (the self rule
+    walks all the pairs of the model).  By the references alone the blocked share lies strictly between 10 % and 90 %, at most 2 % in the band."""
+    eng = _eng_model(which, "caps24", _small_model_back)
+    c = SH.edge_case(which, "full64", 1, "caps24")
+    if rule == "both":
+        SH.with_self_rule(c)
+    assert 4 * (len(c["world"]) * 16 + 64 * ((6 * len(RH.capsules(which, "caps24"))) | 1)) == 41216
+    eng.set_world(c["world"], c["world_thr"])
+    v = SH.case_verdicts(c, rule)
+    assert SH.shares_hold(v), SH.shares(v)
+    for n in (1, 63, 64, 65, SH.N_EDGES_LARGE):
+        out = _sweep(eng, c["a"][:n], c["b"][:n], 1, reject_self=rule == "both", self_min=c["self_thr"] or 0.0)
+        assert set(np.unique(out["blocked"])) <= {0, 1} and ((out["first"] >= -1) & (out["first"] < 1)).all()
+        SH.check_edges(out["blocked"], out["first"], SH.case_verdicts(c, rule, n), f"{which} full64 caps24 {rule} n {n}")
+    print(f"{which} full64 caps24 {rule}: {int(out['blocked'].sum())} of {len(out['blocked'])} edges blocked, shares (band, blocked, free) {SH.shares(v)}")
+
+
+def test_swept_lattice_with_24_capsules(_small_model_back):
+    """k_path_lattice<7, true> with the 24-capsule model, the world and the self rule: the node costs are ikf_rank_candidates' row scores of the same
+    rows under the same world, bit for bit; the path is the masked numpy lattice's on the verdicts of ikf_sweep_edges; blocked and free edges
+    between admissible nodes both occur."""
+    which, T, k, S = SH.LARGE_LATTICE
+    L = SH.lattice_inputs(which, T, k, SH.LARGE_LATTICE_SEED, "caps24")
+    eng = _eng_model(which, "caps24", _small_model_back)
+    eng.set_world(L["world"], L["world_thr"])
+    opt = _popt(collisions=True, min_clearance=L["self_thr"])
+    eng.set_path_sweep(S)
+    out = _path(eng, L["poses"], L["q"], k, opt)
+    _check_nodes_are_rank_scores(eng, out, L["poses"], L["q"], k, opt)
+    sure = (np.abs(L["world_cl"] - L["world_thr"]) > SH.BAND) & (np.abs(L["self_cl"] - L["self_thr"]) > SH.BAND)
+    rejected = (L["world_cl"] < L["world_thr"]) | (L["self_cl"] < L["self_thr"])
+    assert np.array_equal(np.isposinf(out["node"])[sure], rejected[sure]) and 0 < rejected[sure].sum() < sure.sum()
+    ef, sf = _mask_of(eng, L["q"], T, k, S, opt, None)
+    _check_against_masked_dp(out, L["q"], T, k, opt, ef, sf, None, "caps24 lattice")
+    nb, nf = _admissible_edge_counts(out["node"], ef, sf, T, k)
+    print(f"caps24 lattice: {nb} blocked and {nf} free edges between admissible nodes")
+    assert nb > 0 and nf > 0 and np.isfinite(out["cost"][0])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import rank_helpers as RH
 import sweep_helpers as SH
 from test_kin_math_host import _chain_bytes
 from test_world_math_host import _set_capsules, _structs
@@ -133,3 +134,45 @@ def test_mask_geometry(host_lib):
             packed[j // 64] |= np.uint64(1) << np.uint64(j % 64)
         assert [host_lib.sweep_host_bit(packed.ctypes.data, j) for j in range(k)] == [int(x) for x in bits]
     assert [host_lib.sweep_host_pair_waves(n) for n in (0, 1, 63, 64, 65, 257)] == [0, 1, 1, 1, 2, 5]
+
+
+# ---- the 24-capsule model (rank_helpers.capsule_models) -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["syn4r", "syn6r", "fetch"])
+def test_verdicts_with_24_capsules_in_the_64_obstacle_scene(host_lib, which):
+    """The edges of tests/test_sweep.py's 24-capsule cases through the kernel source, under the world rule and under both rules: exact outside the
+    band.  From the references alone: the blocked share lies strictly between 10 % and 90 %, at most 2 % of the edges are in the band."""
+    robot, _ = H.kin_robots(which)
+    chain = _chain_bytes(robot, host_lib)
+    _set_capsules(host_lib, robot, RH.capsules(which, "caps24"))
+    c = SH.with_self_rule(SH.edge_case(which, "full64", 1, "caps24"))
+    assert host_lib.sweep_host_set_world(_structs(c["world"].obstacles), len(c["world"])) == 0
+    for rule in ("world", "both"):
+        v = SH.case_verdicts(c, rule)
+        first = _first(host_lib, chain, c, rule)
+        SH.check_edges(first >= 0, first, v, f"{which} full64 caps24 {rule}")
+        band, blocked, free = SH.shares(v)
+        print(f"{which} full64 caps24 {rule}: seed {SH.LARGE_SEEDS.get(which, 0)}, band {band:.3f} blocked {blocked:.3f} free {free:.3f}")
+        assert SH.shares_hold(v), (which, rule, band, blocked, free)
+
+
+def test_the_swept_lattice_of_the_24_capsule_model_holds_blocked_and_free_edges(host_lib):
+    """The condition tests/test_sweep.py's 24-capsule lattice rests on: with the nodes the references admit and the kernel source's verdicts of
+    every edge, a swept path exists and the edges between admissible nodes hold blocked and free ones."""
+    which, T, k, S = SH.LARGE_LATTICE
+    robot, _ = H.kin_robots(which)
+    chain = _chain_bytes(robot, host_lib)
+    _set_capsules(host_lib, robot, RH.capsules(which, "caps24"))
+    L = SH.lattice_inputs(which, T, k, SH.LARGE_LATTICE_SEED, "caps24")
+    assert host_lib.sweep_host_set_world(_structs(L["world"].obstacles), len(L["world"])) == 0
+    a, b = SH.lattice_edges(L["q"].numpy(), T, k)
+    first = np.full(a.shape[0], -7, np.int32)
+    assert host_lib.sweep_host_edges(chain, a.ctypes.data, b.ctypes.data, a.shape[0], S, 1, L["world_thr"], 1, L["self_thr"], first.ctypes.data) == 0
+    ef, _ = SH.split_lattice_verdicts(first < 0, T, k, False)
+    rejected = (L["world_cl"] < L["world_thr"]) | (L["self_cl"] < L["self_thr"])
+    node = np.where(rejected, np.inf, 0.0).astype(np.float32)
+    adm = ~rejected.reshape(k, T)
+    both = adm.T[1:, :, None] & adm.T[:-1, None, :]
+    nb, nf = int((~ef[1:] & both).sum()), int((ef[1:] & both).sum())
+    cost = SH.dp_f32_masked(L["q"].numpy(), node, T, k, ef)[2]
+    print(f"caps24 lattice seed {SH.LARGE_LATTICE_SEED}: {int(rejected.sum())} of {k * T} nodes rejected, {nb} blocked and {nf} free edges between admissible nodes")
+    assert 0 < rejected.sum() < k * T and nb > 0 and nf > 0 and np.isfinite(cost)

@@ -18,7 +18,7 @@ import rank_helpers as RH
 import world_helpers as WH
 from ikflow_amd import _lib
 from ikflow_amd.world import World
-from test_ranked import _check_selection, _opt, _rank
+from test_ranked import _check_selection, _check_the_straddle, _eng_with, _opt, _rank, _small_model_back  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -399,3 +399,115 @@ def test_status_codes_name_the_obstacle_and_leave_the_world_as_it_was():
     with pytest.raises(Exception, match="at most 64 obstacles"):
         eng.set_world([good] * 65)
     torch.cuda.synchronize()
+
+
+# ---- 9. every capsule count: the LDS slices of k_world_clearance at their maximum, of the ranking with a world around its opt-in -------------
+def _eng_model(which, model, used):
+    eng = _eng_with(which, model, used)
+    if eng not in _USED:
+        _USED.append(eng)
+    return eng
+
+
+@pytest.mark.parametrize("name", ["mixed7", "full64"])
+@pytest.mark.parametrize("which", RH.CASE_CHAINS)
+def test_world_clearance_with_24_capsules(which, name, _small_model_back):
+    """k_world_clearance with the 24-capsule model on chains of 4, 7 and 8 joints; with the 64 obstacles of full64 its dynamic LDS is at the
+    maximum, 41216 B.  1, 63, 64, 65 and 66 rows against the fp64 reference, as test_world_clearance_against_the_fp64_reference."""
+    eng = _eng_model(which, "caps24", _small_model_back)
+    world = WH.scene(which, name, "caps24")
+    q, ref, thr = WH.rows_and_reference(which, name, "caps24")
+    eng.set_world(world, thr)
+    assert eng.world_size == len(world) and 4 * (len(world) * 16 + 64 * ((6 * 24) | 1)) == (41216 if name == "full64" else 37568)
+    assert len(set(ref["capsule"].tolist())) >= 5 and ref["capsule"].max() >= 16   # (the closest capsule changes with the row, late ones among them)
+    for n in (1, 63, 64, 65, 66):
+        _check_against_reference(_clearance(eng, q[:n]), ref, thr, n, f"{which} {name} caps24")
+
+
+@pytest.mark.parametrize("which", RH.CASE_CHAINS)
+def test_world_clearance_without_capsules(which, _small_model_back):
+    """A model of no capsules (a slice of one float per thread): 3.0e38, no pair and no flag on every row, every element written."""
+    eng = _eng_model(which, "caps0", _small_model_back)
+    q = WH.rows_and_reference(which, "mixed7")[0]
+    eng.set_world(WH.scene(which, "mixed7"), 0.05)
+    for n in (1, 64, 130):
+        out = _clearance(eng, q[:n])
+        assert (out["clearance"] == np.float32(3.0e38)).all() and (out["obstacle"] == -1).all() and (out["capsule"] == -1).all() and (out["colliding"] == 0).all()
+
+
+WORLD_MODELS = ("caps11", "caps12", "caps24")
+
+
+def _world_rank_case(which, model):
+    """The tile64 case of rank_helpers.capsule_case with the reference world clearances of its rows in the scene built for the model
+    -> (case, world, world clearances, world threshold)."""
+    seed = RH.CASE_SEEDS.get((which, model, "tile64"), 0)
+    c = RH.capsule_case(which, model, "tile64")
+    poses, q, _, cl, thr = WH.rank_case(which, c["m"], c["k"], model, seed)
+    assert torch.equal(q, c["q"]) and torch.equal(poses, c["poses"])
+    return c, WH.scene(which, WH.RANK_SCENE, model), cl, thr
+
+
+@pytest.mark.parametrize("model", WORLD_MODELS)
+@pytest.mark.parametrize("which", RH.CASE_CHAINS)
+def test_ranking_with_a_world_around_the_opt_in_line(which, model, _small_model_back):
+    """k_rank_candidates<.., WORLD> with 11 capsules (46848 B of LDS: under the opt-in line), 12 (49920 B: over it) and 24 (86784 B, the documented
+    maximum), tile 64 and capacity 16, with and without reject_collisions: row scores by check_row_scores against the reference with the world
+    term, the selection bit for bit."""
+    orob = H.kin_robots(which)[1]
+    c, world, cl, thr = _world_rank_case(which, model)
+    m, k, n_keep = c["m"], c["k"], c["n_keep"]
+    caps = RH.capsules(which, model)
+    eng = _eng_model(which, model, _small_model_back)
+    eng.set_world(world, thr)
+    lds = RH.rank_lds_bytes(m, n_keep, len(caps), world=True)
+    _check_the_straddle(model, m, n_keep, lds, world=True)
+    assert lds == {"caps11": 46848, "caps12": 49920, "caps24": 86784}[model]
+    for collisions in (False, True):
+        self_thr = c["min_clearance"] if collisions else 0.0
+        ref = WH.rank_reference(orob, caps, cl, thr, c["poses"], c["q"], k, 0.01, self_collisions=collisions, min_clearance=self_thr,
+                                self_clearance=c["clearance"])
+        assert RH.shares_hold(ref), (which, model, collisions, RH.shares(ref))
+        out = _rank(eng, c["poses"], c["q"], k, _opt(n_keep=n_keep, collisions=collisions, min_clearance=self_thr))
+        worst = RH.check_row_scores(out["row_score"], ref, f"{which} {model} collisions {collisions}")
+        _check_selection(out, c["q"], m, k, n_keep, f"{which} {model} collisions {collisions}")
+        print(f"ranking with a world {which} {model} collisions {collisions}: {lds} B of LDS, worst {worst:.3f} of eps, shares {RH.shares(ref)}")
+
+
+_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np, torch
+import rank_helpers as RH, world_helpers as WH
+import test_world as TW
+from test_ranked import _opt, _rank, OUTPUTS
+d = np.load(sys.argv[2])
+which, model = "panda", "caps24"
+eng = TW._eng_with(which, model, [])
+eng.set_world(WH.scene(which, WH.RANK_SCENE, model), float(d["thr"]))
+out = _rank(eng, torch.tensor(d["poses"]), torch.tensor(d["q"]), int(d["k"]), _opt(n_keep=int(d["n_keep"]), collisions=True, min_clearance=float(d["self_thr"])))
+np.savez(sys.argv[3], **out)
+print("child ok")
+"""
+
+
+def test_the_24_capsule_world_call_as_the_first_ranking_call_of_a_process(tmp_path, _small_model_back):
+    """The opt-in for more than 48 KiB of dynamic LDS is taken once per process and kernel: only in a fresh process is the largest call (86784 B)
+    the first one.  The child's outputs have the bits of the same call in this process, which has ranked many smaller calls before."""
+    import os
+    import subprocess
+    import sys
+
+    which, model = "panda", "caps24"
+    c, world, cl, thr = _world_rank_case(which, model)
+    eng = _eng_model(which, model, _small_model_back)
+    eng.set_world(world, thr)
+    here = _rank(eng, c["poses"], c["q"], c["k"], _opt(n_keep=c["n_keep"], collisions=True, min_clearance=c["min_clearance"]))
+    assert 0 < np.isposinf(here["row_score"]).sum() < len(here["row_score"])
+    tests = os.path.dirname(os.path.abspath(__file__))
+    np.savez(tmp_path / "in.npz", poses=c["poses"].numpy(), q=c["q"].numpy(), k=c["k"], n_keep=c["n_keep"], thr=thr, self_thr=c["min_clearance"])
+    r = subprocess.run([sys.executable, "-c", _CHILD, tests, str(tmp_path / "in.npz"), str(tmp_path / "out.npz")], capture_output=True, text=True,
+                       timeout=120, cwd=os.path.dirname(tests))
+    assert r.returncode == 0 and "child ok" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+    there = np.load(tmp_path / "out.npz")
+    assert all(H.same_bits(there[n], here[n]) for n in here), [n for n in here if not H.same_bits(there[n], here[n])]

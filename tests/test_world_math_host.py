@@ -183,16 +183,18 @@ def test_ties_go_to_the_lower_obstacle_then_the_lower_capsule(host_lib):
     assert _hit(host_lib, [sph], np.zeros((0, 6)), [])[1:] == (-1, -1)          # no capsules
 
 
-def _set_capsules(lib, robot):
-    robot.set_collision_capsules(RH.collision_capsules(robot))
+def _set_capsules(lib, robot, caps=None):
+    """caps: a capsule list (None: the small model)."""
+    robot.set_collision_capsules(RH.collision_capsules(robot) if caps is None else caps)
     folded, pairs = robot._collision_model
-    arr = (_lib.ikf_capsule * len(folded))()
+    arr = (_lib.ikf_capsule * max(len(folded), 1))()
     for c, (frame, p0, p1, r) in zip(arr, folded):
         c.frame, c.radius = int(frame), float(r)
         for i in range(3):
             c.p0[i], c.p1[i] = float(p0[i]), float(p1[i])
-    flat = (C.c_int32 * (2 * len(pairs)))(*[int(v) for ab in pairs for v in ab])
+    flat = (C.c_int32 * max(2 * len(pairs), 1))(*[int(v) for ab in pairs for v in ab])
     lib.world_host_set_capsules(arr, len(folded), flat, len(pairs))
+    robot.set_collision_capsules(RH.collision_capsules(robot))   # (the robots are shared: the small model is back)
 
 
 def _rows(lib, chain, q):
@@ -260,3 +262,67 @@ def test_row_scores_with_the_world_rule(host_lib, which):
         RH.check_row_scores(out, ref, f"{which} collisions {collisions}")
         plain = WH.rank_reference(orob, caps, None, 0.0, poses, q, k, 0.01, self_collisions=collisions, min_clearance=self_thr)
         assert (plain["admissible"] & ~ref["admissible"]).sum() > 0.1 * k * m   # (the world rule does reject rows of its own)
+
+
+# ---- the capsule models by size (rank_helpers.capsule_models) -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["mixed7", "full64"])
+@pytest.mark.parametrize("which", RH.CASE_CHAINS)
+def test_whole_rows_with_24_capsules(host_lib, which, name):
+    """The 66 rows of tests/test_world.py's 24-capsule cases through the kernel source: within 2e-5 of the fp64 reference, the closest pair the
+    reference's - and it is a capsule behind the 16th on some rows.  From the reference alone: at most 2 % of the rows in the band around the
+    threshold, the share below it strictly between 10 % and 90 %."""
+    robot, _ = H.kin_robots(which)
+    chain = _chain_bytes(robot, host_lib)
+    _set_capsules(host_lib, robot, RH.capsules(which, "caps24"))
+    world = WH.scene(which, name, "caps24")
+    q, ref, thr = WH.rows_and_reference(which, name, "caps24")
+    assert host_lib.world_host_set_world(_structs(world.obstacles), len(world)) == 0
+    cl, ob, cp = _rows(host_lib, chain, q)
+    err = float(np.abs(cl - ref["clearance"]).max())
+    band, below, above = WH.band_shares(ref["clearance"], thr)
+    print(f"{which} {name} caps24: worst {err:.2e}, threshold {thr:.4f}, band {band:.3f} below {below:.3f} above {above:.3f}, "
+          f"closest capsules {sorted(set(ref['capsule'].tolist()))}")
+    assert err <= TOL, (which, name, err)
+    sure = ~ref["ambiguous"]
+    assert np.array_equal(ob[sure], ref["obstacle"][sure]) and np.array_equal(cp[sure], ref["capsule"][sure]), (which, name)
+    assert band <= 0.02 and 0.1 < below < 0.9, (which, name, band, below)
+    assert len(set(ref["capsule"].tolist())) >= 5 and ref["capsule"].max() >= 16
+
+
+def test_whole_rows_without_capsules(host_lib):
+    for which in RH.CASE_CHAINS:
+        robot, _ = H.kin_robots(which)
+        chain = _chain_bytes(robot, host_lib)
+        _set_capsules(host_lib, robot, [])
+        world = WH.scene(which, "mixed7")
+        assert host_lib.world_host_set_world(_structs(world.obstacles), len(world)) == 0
+        cl, ob, cp = _rows(host_lib, chain, WH.rows_and_reference(which, "mixed7")[0][:65])
+        assert (cl == np.float32(3.0e38)).all() and (ob == -1).all() and (cp == -1).all()
+
+
+@pytest.mark.parametrize("model", ["caps11", "caps12", "caps24"])
+@pytest.mark.parametrize("which", RH.CASE_CHAINS)
+def test_row_scores_with_the_world_rule_and_the_large_models(host_lib, which, model):
+    """rank_row_score_world on the rows of tests/test_world.py's ranking around the opt-in line, with and without reject_collisions; and the
+    condition from the references alone: inadmissible share strictly between 10 % and 90 %, at most 2 % of the rows inside a band."""
+    robot, orob = H.kin_robots(which)
+    chain = _chain_bytes(robot, host_lib)
+    caps = RH.capsules(which, model)
+    _set_capsules(host_lib, robot, caps)
+    world = WH.scene(which, WH.RANK_SCENE, model)
+    assert host_lib.world_host_set_world(_structs(world.obstacles), len(world)) == 0
+    c = RH.capsule_case(which, model, "tile64")
+    m, k = c["m"], c["k"]
+    poses, q, _, cl, thr = WH.rank_case(which, m, k, model, RH.CASE_SEEDS.get((which, model, "tile64"), 0))
+    assert (q == c["q"]).all()
+    for collisions in (False, True):
+        self_thr = c["min_clearance"] if collisions else 0.0
+        opt = _lib.ikf_rank_options(1, 0.01, 0.0, -1.0, -1.0, 0, int(collisions), self_thr)
+        out = np.zeros(k * m, np.float32)
+        pn, qn = np.ascontiguousarray(poses.numpy()), np.ascontiguousarray(q.numpy())
+        assert host_lib.world_host_scores(chain, C.byref(opt), pn.ctypes.data, qn.ctypes.data, m, k, thr, out.ctypes.data) == 0
+        ref = WH.rank_reference(orob, caps, cl, thr, poses, q, k, 0.01, self_collisions=collisions, min_clearance=self_thr, self_clearance=c["clearance"])
+        RH.check_row_scores(out, ref, f"{which} {model} collisions {collisions}")
+        near, bad = RH.shares(ref)
+        print(f"host world ranking {which} {model} collisions {collisions}: near-band share {near:.4f}, inadmissible share {bad:.4f}")
+        assert RH.shares_hold(ref), (which, model, collisions, near, bad)

@@ -157,15 +157,16 @@ _KINDS = {"sphere": [SPHERE], "capsule": [CAPSULE], "half_space": [HALF_SPACE], 
 _SCENE_CACHE = {}
 
 
-def scene(which, name):
-    """The World `name` for chain `which` (fixed seeds).  Obstacles sit where the robot's moving capsules pass - around end points of those
-    capsules at random configurations, in the outer half of the reach - so that clearances spread over decimetres with both signs."""
-    if (which, name) in _SCENE_CACHE:
-        return _SCENE_CACHE[(which, name)]
+def scene(which, name, caps=None):
+    """The World `name` for chain `which` (fixed seeds) and its capsule model `caps` (a name of rank_helpers.capsule_models; None: the small
+    model of rank_helpers.collision_capsules).  Obstacles sit where the robot's moving capsules pass - around end points of those capsules at
+    random configurations, in the outer half of the reach - so that clearances spread over decimetres with both signs."""
+    if (which, name, caps) in _SCENE_CACHE:
+        return _SCENE_CACHE[(which, name, caps)]
     import helpers as H
 
     robot, orob = H.kin_robots(which)
-    caps = RH.collision_capsules(robot)
+    caps_name, caps = caps, RH.capsules(which, caps)
     rng = np.random.default_rng(7000 + 13 * SCENES.index(name) + sum(map(ord, which)))
     qs = torch.tensor(orob.sample_joint_angles(256, 0.0, np.random.default_rng(77)))
     E0, E1, radii = capsule_ends(orob, caps, qs)
@@ -189,13 +190,15 @@ def scene(which, name):
                 ob = (BOX, c, rng.uniform(0.02, 0.25, 3), rng.standard_normal(4) * rng.uniform(0.5, 2.0), 0.0 if i % 2 == 0 else rng.uniform(0.005, 0.04))
             # The base capsule does not move: its clearance is the same in every row.  An obstacle is kept only when the moving capsules come
             # closer than that in three quarters of the sampled configurations, so that no threshold (a median) can sit on that constant.
-            d = pair_clearance(ob, E0[::4], E1[::4], radii[None, :])
+            # (every 4th of the sampled configurations; every 16th with a model of rank_helpers.capsule_models, whose 24 capsules cost five times as much)
+            every = 4 if caps_name is None else 16
+            d = pair_clearance(ob, E0[::every], E1[::every], radii[None, :])
             if d[0, 0] > np.quantile(d[:, 1:].min(1), 0.75):
                 break
         else:
             raise AssertionError(f"scene {name} of {which}: no place found for obstacle {i}")
         w._add(*ob)
-    _SCENE_CACHE[(which, name)] = w
+    _SCENE_CACHE[(which, name, caps_name)] = w
     return w
 
 
@@ -210,20 +213,22 @@ def far_world():
 
 
 N_ROWS = 257
+N_ROWS_LARGE = 66     # with a capsule model of rank_helpers.capsule_models: the reference's cost grows with capsules x obstacles
 _ROWS_CACHE = {}
 
 
-def rows_and_reference(which, name):
+def rows_and_reference(which, name, caps=None):
     """The 257 configurations (inside the limits, f32) on which chain `which` meets scene `name`, their fp64 reference and the scene's threshold
-    (the median of these rows' clearances) - computed once; the GPU tests run slices rows[:n] of them."""
-    if (which, name) not in _ROWS_CACHE:
+    (the median of these rows' clearances) - computed once; the GPU tests run slices rows[:n] of them.  caps: a name of
+    rank_helpers.capsule_models (then 66 rows: one workgroup and two threads), None: the small model."""
+    if (which, name, caps) not in _ROWS_CACHE:
         import helpers as H
 
         robot, orob = H.kin_robots(which)
-        q = torch.tensor(orob.sample_joint_angles(N_ROWS, 0.0, np.random.default_rng(300))).float().contiguous()
-        ref = reference(orob, RH.collision_capsules(robot), scene(which, name), q)
-        _ROWS_CACHE[(which, name)] = (q, ref, threshold(ref["clearance"]))
-    return _ROWS_CACHE[(which, name)]
+        q = torch.tensor(orob.sample_joint_angles(N_ROWS if caps is None else N_ROWS_LARGE, 0.0, np.random.default_rng(300))).float().contiguous()
+        ref = reference(orob, RH.capsules(which, caps), scene(which, name, caps), q)
+        _ROWS_CACHE[(which, name, caps)] = (q, ref, threshold(ref["clearance"]))
+    return _ROWS_CACHE[(which, name, caps)]
 
 
 # The ranking with a world: one scene, the shapes of tests/test_world.py, and per (chain, shape) the candidates with their reference clearances
@@ -234,23 +239,26 @@ RANK_SHAPES = [(1, 1), (3, 5), (65, 2), (64, 16), (1, 1024)]
 _RANK_CASES = {}
 
 
-def rank_case(which, m, k):
-    """-> (poses, q, q_ref, reference world clearance of the k * m rows, threshold)."""
-    if (which, m, k) not in _RANK_CASES:
+def rank_case(which, m, k, caps=None, seed=None):
+    """-> (poses, q, q_ref, reference world clearance of the k * m rows, threshold).  caps: a name of rank_helpers.capsule_models (the scene is
+    then the one built for that model), None: the small model; seed: of the candidates, m + k by default."""
+    if (which, m, k, caps, seed) not in _RANK_CASES:
         import helpers as H
 
         robot, orob = H.kin_robots(which)
         # (noise from 0.03 rad up: with the family's 0.001 rad a third of one pose's 1024 candidates would share a clearance to within the band)
-        poses, q, q_ref = RH.candidates(orob, m, k, seed=m + k, lo_exp=-1.5)
-        cl = reference(orob, RH.collision_capsules(robot), scene(which, RANK_SCENE), q)["clearance"]
-        _RANK_CASES[(which, m, k)] = (poses, q, q_ref, cl, threshold(cl))
-    return _RANK_CASES[(which, m, k)]
+        poses, q, q_ref = RH.candidates(orob, m, k, seed=m + k if seed is None else seed, lo_exp=-1.5)
+        cl = reference(orob, RH.capsules(which, caps), scene(which, RANK_SCENE, caps), q)["clearance"]
+        _RANK_CASES[(which, m, k, caps, seed)] = (poses, q, q_ref, cl, threshold(cl))
+    return _RANK_CASES[(which, m, k, caps, seed)]
 
 
 # ---- the ranking's reference with the world rule on top ----------------------------------------------------------------------------------------
 def rank_reference(orob, robot_caps, world_cl, world_min_clearance, poses, q, k, rot_weight, self_collisions=False, min_clearance=0.0, **kw):
     """rank_helpers.reference(...) with admissibility extended by `world clearance >= world_min_clearance` and its 1e-4 band; world_cl: the
     reference world clearances of the rows (None: no world)."""
+    if not self_collisions:
+        kw.pop("self_clearance", None)
     ref = RH.reference(orob, poses, q, k, rot_weight, caps=robot_caps if self_collisions else None, min_clearance=min_clearance, **kw)
     if world_cl is not None:
         ref["admissible"] = ref["admissible"] & ~(world_cl < world_min_clearance)
