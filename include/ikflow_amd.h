@@ -116,9 +116,9 @@ ikf_status ikf_reserve_exact(ikf_model* m, int64_t max_poses, int max_repeat);
 ikf_status ikf_set_exact_upfront_rows(ikf_model* m, int64_t max_rows);
 
 /* -- approximate IK: replaces IKFlowSolver._run_inference (ikflow_solver.py:85-110) ----------------------- */
-/* d_poses: [n x 7], or a single pose [7] when pose_broadcast != 0 (the `y.expand((n,7))` form, :333-336).
- * d_latent: [n x D].  d_q_out: [n x ndof].  clamp_to_limits: robot.clamp_to_joint_limits (:101-102).
- * softflow_scale: the 8th conditional entry (always 0.0 at inference, :335-338). */
+/* d_poses: [n x 7], or a single pose [7] when pose_broadcast != 0 (the `y.expand((n,7))` form, :333-336).  d_latent: [n x D].  d_q_out: [n x ndof].
+ * clamp_to_limits: robot.clamp_to_joint_limits (:101-102).  softflow_scale: the 8th conditional entry (always 0.0 at inference, :335-338).
+ * It writes exactly n x ndof floats at d_q_out and nothing else, and needs no alignment beyond 4 bytes for its pointers (tests/test_flow_sample.py). */
 ikf_status ikf_generate_approx(ikf_model* m, const float* d_poses, int pose_broadcast, const float* d_latent,
                                int64_t n, int clamp_to_limits, float softflow_scale, float* d_q_out, void* stream);
 /* GraphINN forward (model.py:300-354): d_x [n x D], d_poses as above -> d_z_out [n x D], d_log_det_out [n], nullable; f32 in either precision */

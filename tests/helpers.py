@@ -56,6 +56,54 @@ def custom_model(nb_nodes=2, dim=9, n_hidden=2, width=256, robot_name="panda", s
     return get_robot(robot_name), hp, lay, fo.make_state_dict(lay, robot_name, seed=seed, output_gain=gain)
 
 
+def _dense_fixed_transform(model, seed):
+    """The builders' state_dicts carry the reference's FixedLinearTransform: diagonal M, b = 0 on plain graphs - neither the bias, the
+    index order of x.mm(M) / (x - b).mm(M_inv) nor the sign of log|det M_inv| shows there.  This one is dense and non-symmetric with b != 0
+    and |det| far from 1 (M_inv the fp64 inverse of the f32 M, both rounded to f32)."""
+    robot, hp, lay, sd = model
+    rng = np.random.default_rng(seed)
+    D = lay.dim
+    M = np.asarray(sd["module_list.0.M"], dtype=np.float64) @ (np.eye(D) + 0.3 * rng.standard_normal((D, D)) / np.sqrt(D))
+    sd = dict(sd)
+    sd["module_list.0.M"] = M.astype(np.float32)
+    sd["module_list.0.M_inv"] = np.linalg.inv(M.astype(np.float32).astype(np.float64)).astype(np.float32)
+    sd["module_list.0.b"] = (0.2 * rng.standard_normal((1, D))).astype(np.float32)
+    return robot, hp, lay, sd
+
+
+def shuffled_permutations(model, seed):
+    """The builders always produce PermuteRandom's np.random.seed(i) tables: an index slip that is right for those tables only stays hidden.
+    Here every block gets another seeded permutation (perm and perm_inv consistent: perm_inv[perm[k]] = k) that differs from its seed-i
+    table, no two blocks share one, and no position is a fixed point of every block."""
+    robot, hp, lay, sd = model
+    rng = np.random.default_rng(seed)
+    D = lay.dim
+    stock = [fo.permute_random_tables(D, i)[0] for i in range(lay.nb_nodes)]
+    while True:
+        perms = [rng.permutation(D).astype(np.int64) for _ in range(lay.nb_nodes)]
+        differs = all(not np.array_equal(p, s) for p, s in zip(perms, stock))
+        distinct = len({p.tobytes() for p in perms}) == len(perms)
+        fixed_everywhere = np.all([p == np.arange(D) for p in perms], axis=0).any()
+        if differs and distinct and not fixed_everywhere:
+            break
+    sd = dict(sd)
+    for i, perm in enumerate(perms):
+        perm_inv = np.empty_like(perm)
+        perm_inv[perm] = np.arange(D)
+        sd[f"module_list.{lay.perm_module(i)}.perm"] = perm
+        sd[f"module_list.{lay.perm_module(i)}.perm_inv"] = perm_inv
+    return robot, hp, lay, sd
+
+
+def plain_bias(model, seed):
+    """A non-zero module_list.0.b on a plain (non-sigmoid) graph, whose builder leaves it at zero; M and M_inv stay as they are."""
+    robot, hp, lay, sd = model
+    assert not lay.sigmoid_on_output
+    sd = dict(sd)
+    sd["module_list.0.b"] = (0.2 * np.random.default_rng(seed).standard_normal((1, lay.dim))).astype(np.float32)
+    return robot, hp, lay, sd
+
+
 def reachable_poses(robot, n, seed=0, eps=0.004363323129985824):
     """poses = FK(q), q ~ U(lo+eps, hi-eps) (scripts/build_dataset.py:186 convention)."""
     q = torch.tensor(O(robot).sample_joint_angles(n, eps, np.random.default_rng(seed)))

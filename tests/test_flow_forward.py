@@ -13,7 +13,8 @@ import pytest
 import torch
 
 from flow_logdet import fd_logdet, forward_with_logdet
-from helpers import O, custom_model, fetch_arm_model, latents, panda_model, reachable_poses, released_model, tiny_model
+from helpers import (O, _dense_fixed_transform, custom_model, fetch_arm_model, latents, panda_model, reachable_poses, released_model,
+                     tiny_model)
 from ikflow_amd import _lib
 from ikflow_amd.ikflow_solver import IKFlowSolver
 from oracle import flow_oracle as fo
@@ -500,20 +501,6 @@ def test_state_dict_without_M(which):
     x, poses, _ = _rows(model, n, 95)
     z, ld = eng.flow_forward(x.to(DEV), poses.to(DEV))
     _check(f"{which} without M", sd, lay, x, _cond(lay, poses.numpy()), z, ld)
-
-
-def _dense_fixed_transform(model, seed):
-    """The builders' state_dicts carry the reference's FixedLinearTransform: diagonal M, b = 0 on plain graphs - neither the bias nor
-    the index order of x.mm(M) shows there.  This one is dense and non-symmetric with b != 0 (M_inv its fp64 inverse, both rounded to f32)."""
-    robot, hp, lay, sd = model
-    rng = np.random.default_rng(seed)
-    D = lay.dim
-    M = np.asarray(sd["module_list.0.M"], dtype=np.float64) @ (np.eye(D) + 0.3 * rng.standard_normal((D, D)) / np.sqrt(D))
-    sd = dict(sd)
-    sd["module_list.0.M"] = M.astype(np.float32)
-    sd["module_list.0.M_inv"] = np.linalg.inv(M.astype(np.float32).astype(np.float64)).astype(np.float32)
-    sd["module_list.0.b"] = (0.2 * rng.standard_normal((1, D))).astype(np.float32)
-    return robot, hp, lay, sd
 
 
 @pytest.mark.gpu

@@ -17,7 +17,8 @@ import pytest
 import torch
 
 from flow_logdet import fd_logdet, forward_with_logdet
-from helpers import O, custom_model, fetch_arm_model, latents, panda_model, reachable_poses, released_model, tiny_model
+from helpers import (O, _dense_fixed_transform, custom_model, fetch_arm_model, latents, panda_model, reachable_poses, released_model,
+                     tiny_model)
 from ikflow_amd import _lib
 from ikflow_amd.ikflow_solver import IKFlowSolver
 from oracle import flow_oracle as fo
@@ -468,21 +469,6 @@ def test_f16x3_precision_leaves_the_call_in_f32(which):
     assert eng.precision == "f16x3"
     got = eng.flow_inverse(Z, P)
     assert all(torch.equal(u, v) for u, v in zip(ref, got))
-
-
-def _dense_fixed_transform(model, seed):
-    """The builders' state_dicts carry the reference's FixedLinearTransform: diagonal M, b = 0 on plain graphs - neither the bias, the
-    index order of (x - b).mm(M_inv) nor the sign of log|det M_inv| shows there.  This one is dense and non-symmetric with b != 0 and
-    |det| far from 1 (M_inv the fp64 inverse of the f32 M, rounded to f32)."""
-    robot, hp, lay, sd = model
-    rng = np.random.default_rng(seed)
-    D = lay.dim
-    M = np.asarray(sd["module_list.0.M"], dtype=np.float64) @ (np.eye(D) + 0.3 * rng.standard_normal((D, D)) / np.sqrt(D))
-    sd = dict(sd)
-    sd["module_list.0.M"] = M.astype(np.float32)
-    sd["module_list.0.M_inv"] = np.linalg.inv(M.astype(np.float32).astype(np.float64)).astype(np.float32)
-    sd["module_list.0.b"] = (0.2 * rng.standard_normal((1, D))).astype(np.float32)
-    return robot, hp, lay, sd
 
 
 @pytest.mark.gpu
