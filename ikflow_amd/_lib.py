@@ -19,6 +19,7 @@ IKF_PATH_MAX_K = 256
 IKF_DIVERSE_MAX_K = 1024
 IKF_DIVERSE_MAX_KEEP = 16
 IKF_WORLD_MAX_OBSTACLES = 64
+IKF_CLOUD_MAX_POINTS = 1 << 20
 IKF_SWEEP_MAX_SAMPLES = 16
 IKF_REFINE_MAX_STEPS = 16
 IKF_OBSTACLE_SPHERE, IKF_OBSTACLE_CAPSULE, IKF_OBSTACLE_HALF_SPACE, IKF_OBSTACLE_BOX = 0, 1, 2, 3
@@ -244,6 +245,15 @@ WORLD_SIGNATURES = {
     "ikf_world_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# ... every symbol include/ikflow_amd_cloud.h declares (world point cloud: the sensed scene as points against the robot's capsules)
+CLOUD_SIGNATURES = {
+    # h_points, n_points, point_radius, min_clearance
+    "ikf_set_world_cloud": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float]),
+    "ikf_world_cloud_size": (C.c_int64, [C.c_void_p]),
+    # q, n, clearance_out, colliding_out, stream
+    "ikf_cloud_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # ... every symbol include/ikflow_amd_sweep.h declares (swept collision checks along edges: the caller's, and those of a path lattice)
 SWEEP_SIGNATURES = {
     "ikf_set_path_sweep": (C.c_int, [C.c_void_p, C.c_int]),
@@ -286,7 +296,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -76,6 +76,16 @@ ikf_status ikf::score_candidates(ikf_model* m, const float* d_poses, int64_t n, 
     a.world_min_clearance = m->world_min_clearance;
   }
   a.cap_stride = (opt.reject_collisions || m->world_n > 0) ? ((m->n_caps * 6) | 1) : 0;
+  // With a point cloud set on the handle (ikf_set_world_cloud) the rows' cloud clearances are computed first, on the same stream, into the
+  // handle's buffer; the ranking kernel reads one float per row.
+  if (m->cloud_n > 0) {
+    const long long rows = n * (long long)k;
+    IKF_HIP(m->cloud_row.ensure(rows));
+    ikf_status st = run_cloud_clearance(m, d_q, rows, m->cloud_row.p, nullptr, s);
+    if (st != IKF_OK) return st;
+    a.cloud_clearance = m->cloud_row.p;
+    a.cloud_min_clearance = m->cloud_min_clearance;
+  }
   a.row_score = d_row_score;
   a.q_out = d_q_out;
   a.score_out = d_score_out;
@@ -139,6 +149,10 @@ ikf_status ikf::reserve_candidates(ikf_model* m, const char* who, const char* ru
   const long long rows = max_poses * (long long)max_k;
   ikf_status st = ensure_rank_rows(m, rows);
   if (st == IKF_OK) st = ensure_rank_lists(m, max_poses);
+  if (st == IKF_OK && m->cloud_n > 0) {   // the rows' cloud clearances and their partial minima, under the cloud that is set now
+    IKF_HIP(m->cloud_row.ensure(rows));
+    st = ensure_cloud_partials(m, rows);
+  }
   if (st == IKF_OK && m->loaded) st = ikf_reserve(m, rows);   // the flow's scratch (and, where that path can be reached, its weight image)
   return st;
 }

@@ -10,6 +10,7 @@
 #include "path_math.h"
 #include "diverse_math.h"
 #include "world_math.h"
+#include "cloud_math.h"
 #include "sweep_math.h"
 #include "refine_math.h"
 #include "flow_plan.h"  // IKF_RO_ROWS, the planner and the cluster back-off (host arithmetic, no HIP)
@@ -444,6 +445,8 @@ struct RankArgs {
   int cap_stride;             // floats of capsule scratch per thread (odd: bank spread), 0 without collisions and without a world
   const WorldModel* world;    // the handle's obstacles (world_math.h), or null: no world rule
   float world_min_clearance;  // read only with a world
+  const float* cloud_clearance;  // [k * m] the rows' cloud clearances (cloud_kernels.hip), or null: no cloud rule
+  float cloud_min_clearance;  // read only with cloud clearances
   float* row_score;           // [k * m], or null
   // one chunk: stage 1 writes the final outputs; more: the partial lists below, merged by k_rank_merge
   float* q_out;               // [m][n_keep][ndof]
@@ -495,6 +498,12 @@ hipError_t launch_diverse_select(int ndof, const DiverseArgs& a, hipStream_t s);
 hipError_t launch_world_clearance(const Chain* d_chain, const CollisionModel* d_cm, int n_caps, const WorldModel* d_world, int n_obs,
                                   float min_clearance, int ndof, const float* q, long long n, float* clearance, int* obstacle, int* capsule,
                                   uint8_t* colliding, hipStream_t s);
+
+// cloud_kernels.hip - world point cloud (include/ikflow_amd_cloud.h; the arithmetic and the plan: cloud_math.h).  pts: the stored points, padded
+// to a multiple of IKF_CLOUD_TILE; n_points == 0: 3.0e38 / 0.  partial: cloud_plan(n, n_points, n_cu).chunks * n floats when that is > 1 chunk.
+hipError_t launch_cloud_clearance(const Chain* d_chain, const CollisionModel* d_cm, int n_caps, const CloudPoint* pts, long long n_points,
+                                  float point_radius, float min_clearance, int ndof, const float* q, long long n, int n_cu, float* clearance,
+                                  uint8_t* colliding, float* partial, hipStream_t s);
 
 // sweep_kernels.hip - swept collision checks along edges (include/ikflow_amd_sweep.h; the arithmetic: sweep_math.h).  ONE kernel, two edge
 // sources: the caller's pairs (lattice == 0: lane = edge i of qa -> qb) and the edges of a path lattice (lattice != 0: one wave per word of

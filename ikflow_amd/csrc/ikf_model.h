@@ -1,6 +1,6 @@
 // The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
 // reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
-// those units (and api_rank / api_path / api_diverse / api_world / api_sweep / api_refine) only; the kernel-launch interface is ikf_internal.h.
+// those units (and api_rank / api_path / api_diverse / api_world / api_cloud / api_sweep / api_refine) only; the kernel-launch interface is ikf_internal.h.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -189,6 +189,12 @@ struct ikf_model {
   DeviceBuf<WorldModel> d_world;  // allocated by the first ikf_set_world with obstacles
   int world_n = 0;
   float world_min_clearance = 0.f;
+  // world point cloud (api_cloud.hip): the sensed scene; with cloud_n > 0 the candidate stage also rejects rows closer than cloud_min_clearance
+  DeviceBuf<CloudPoint> d_cloud;  // [cloud_n rounded up to IKF_CLOUD_TILE] (x, y, z, 0), the padding copies of the last point
+  long long cloud_n = 0;
+  float cloud_radius = 0.f, cloud_min_clearance = 0.f;
+  DeviceBuf<float> cloud_row;     // [rows] the candidate rows' cloud clearances (score_candidates)
+  DeviceBuf<float> cloud_part;    // [chunks][rows] partial minima of a call whose plan has more than one chunk
   // f16x3 range guard
   DeviceBuf<int> d_split_flag;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
   PinnedBuf<int> h_split_flag;    // pinned host
@@ -317,5 +323,9 @@ inline ikf_rank_options scoring_options(const Opt& o) {
 // What ikf_reserve_ranked / _path / _diverse share: the argument test (`rule`: the family's message), candidate rows, partial lists and,
 // with weights loaded, the flow's own reservation.
 ikf_status reserve_candidates(ikf_model* m, const char* who, const char* rule, int64_t max_poses, int max_k, int k_max);
+// The world point cloud (api_cloud.hip): the partial minima a call of `rows` rows needs under the cloud that is set (nothing without one), and the
+// launch of k_cloud_clearance on the handle's cloud - both outputs nullable, the caller holds the stream scope.
+ikf_status ensure_cloud_partials(ikf_model* m, long long rows);
+ikf_status run_cloud_clearance(ikf_model* m, const float* d_q, long long rows, float* d_clearance, uint8_t* d_colliding, hipStream_t s);
 }  // namespace ikf
 #pragma GCC visibility pop

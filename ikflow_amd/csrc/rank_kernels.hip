@@ -13,7 +13,8 @@
 // floats of capsule end points when collisions are rejected (<= 74240 B at 24 capsules): at most 82688 B of a CU's 160 KiB.
 // WORLD (a world is set on the handle, include/ikflow_amd_world.h): the obstacle table (4096 B) is staged between the two areas, every
 // thread has its capsule slice whatever reject_collisions says, and the score is rank_row_score_world: at most 86784 B.  WORLD = false is the
-// kernel as it was.
+// kernel as it was.  A point cloud on the handle (include/ikflow_amd_cloud.h) costs both forms one run-time test of a pointer per row: with
+// RankArgs::cloud_clearance set, a row whose precomputed cloud clearance is below the cloud's threshold scores +inf before anything sees its score.
 #include "ikf_internal.h"
 
 namespace ikf {
@@ -71,6 +72,8 @@ __global__ __launch_bounds__(IKF_RANK_BLOCK) void k_rank_candidates(const RankAr
       float score;
       if constexpr (WORLD) score = rank_row_score_world<NDOF>(a.ch, a.cm, qv, tg, qr, a.q_ref != nullptr, a.opt, w, obs, n_obs, a.world_min_clearance);
       else score = rank_row_score<NDOF>(a.ch, a.cm, qv, tg, qr, a.q_ref != nullptr, a.opt, w);
+      // a point cloud on the handle (include/ikflow_amd_cloud.h): the row's clearance from it was computed in front of this launch
+      if (a.cloud_clearance && a.cloud_clearance[row] < a.cloud_min_clearance) score = rank_inf();
       if (a.row_score) a.row_score[row] = score;
       if (score < rank_inf()) ++count;
       top.insert(score, r);

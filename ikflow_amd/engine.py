@@ -391,6 +391,37 @@ class Engine:
                                                   col.data_ptr(), self._stream()))
         return dist, obstacle, capsule, col.to(torch.bool)
 
+    # -- world point cloud (include/ikflow_amd_cloud.h) --------------------------------------------------------
+    def set_world_cloud(self, points, point_radius: float, min_clearance: float = 0.0) -> None:
+        """points: [n x 3] (numpy or torch, any device; at most 2^20; an empty one clears) in the base frame, each a sphere of point_radius.
+        While a cloud is set, rank_candidates / generate_ranked, path_search / generate_path and diverse_select / generate_diverse also drop
+        every candidate whose cloud clearance is below min_clearance - beside whatever set_world set; the sweep does not test the cloud.  Not
+        while calls on this engine are in flight on another stream."""
+        if isinstance(points, torch.Tensor):
+            points = points.detach().cpu().numpy()
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
+        if len(pts) > _lib.IKF_CLOUD_MAX_POINTS:
+            raise EngineError(f"a cloud holds at most {_lib.IKF_CLOUD_MAX_POINTS} points, got {len(pts)}")
+        self._ck(self.lib.ikf_set_world_cloud(self._h, pts.ctypes.data if len(pts) else None, len(pts), float(point_radius), float(min_clearance)))
+
+    def clear_world_cloud(self) -> None:
+        self._ck(self.lib.ikf_set_world_cloud(self._h, None, 0, 0.0, 0.0))
+
+    @property
+    def world_cloud_size(self) -> int:
+        return int(self.lib.ikf_world_cloud_size(self._h))
+
+    def cloud_clearance(self, q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """[n x ndof] -> (signed clearance of the closest (capsule, point) [n] f32 - 3.0e38 with an empty cloud -, clearance < the cloud's
+        min_clearance [n] bool)."""
+        q = self._q(q)
+        n = q.shape[0]
+        dist = torch.empty(n, dtype=torch.float32, device=self.device)
+        col = torch.empty(n, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_cloud_clearance(self._h, q.data_ptr(), n, dist.data_ptr(), col.data_ptr(), self._stream()))
+        return dist, col.to(torch.bool)
+
     # -- swept collision checks along edges (include/ikflow_amd_sweep.h) ------------------------------------
     def set_path_sweep(self, n_samples: int) -> None:
         """Samples per lattice edge of path_search / generate_path (0: no sweep, the default; at most 16).  While a sweep is set, an edge

@@ -130,6 +130,7 @@ class IKFlowSolver:
         self._model_weights_loaded = False
         self._engine = None  # created on first use, on the device of the inputs
         self._world = None   # (World, min_clearance) of set_world: re-applied to every engine this solver creates
+        self._world_cloud = None  # (points [n x 3] host f32, point_radius, min_clearance) of set_world_cloud: likewise
         self._path_sweep = 0  # samples per lattice edge of set_path_sweep: likewise
         self._candidate_refine = (0, 0.0, 0.0)  # (n_steps, pos_tol, rot_tol) of set_candidate_refine: likewise
         # tests / tools only: "probes" binds lib/libikflow_amd_probes.so (the product + the priced-and-rejected forms of rounds 2 - 3);
@@ -180,6 +181,8 @@ class IKFlowSolver:
                     raise
             if self._world is not None:
                 self._push_world(eng)
+            if self._world_cloud is not None:
+                self._push_world_cloud(eng)
             if self._path_sweep:
                 eng.set_path_sweep(self._path_sweep)
             if self._candidate_refine[0]:
@@ -209,11 +212,46 @@ class IKFlowSolver:
         else:
             self.engine()
 
-    def _push_world(self, eng):
+    def _push_collision_model(self, eng):
         if getattr(eng, "_collision_source", None) is not self._robot._collision_model:
             eng.set_collision_model(*self._robot._collision_model)   # the solver's own handle, not the one Robot.config_self_collides uses
             eng._collision_source = self._robot._collision_model
+
+    def _push_world(self, eng):
+        self._push_collision_model(eng)
         eng.set_world(*self._world)
+
+    def set_world_cloud(self, points, point_radius: float, min_clearance: float = 0.0):
+        """The sensed scene as points ([n x 3], numpy or torch on any device, base frame; at most 2^20; None or an empty one: no cloud), each a
+        sphere of point_radius.  While a cloud is set, generate_ranked_ik_solutions, generate_ik_path and generate_diverse_ik_solutions also drop
+        every candidate whose clearance from a point is below min_clearance - whatever reject_self_collisions says, and beside a world of
+        set_world.  The swept edges of set_path_sweep do not test the cloud.  Needs the robot's capsule model (Robot.set_collision_capsules)."""
+        for name, v in (("point_radius", point_radius), ("min_clearance", min_clearance)):
+            assert isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v), f"{name} must be a finite number, got {v!r}"
+        assert point_radius >= 0, f"point_radius must be >= 0, got {point_radius!r}"
+        if points is not None:
+            if isinstance(points, torch.Tensor):
+                points = points.detach().cpu().numpy()
+            points = np.asarray(points)
+            assert points.size == 0 or (points.ndim == 2 and points.shape[1] == 3), f"points must be [n x 3], got {tuple(points.shape)}"
+            points = np.ascontiguousarray(points.reshape(-1, 3), dtype=np.float32)
+            assert len(points) <= 1 << 20, f"a cloud holds at most {1 << 20} points, got {len(points)}"
+            assert bool(np.isfinite(points).all()), "points must be finite"
+        if points is None or len(points) == 0:
+            self._world_cloud = None
+            if self._engine is not None:
+                self._engine.clear_world_cloud()
+            return
+        assert self._robot.has_collision_model, "set_world_cloud needs a collision model (Robot.set_collision_capsules)"
+        self._world_cloud = (points, float(point_radius), float(min_clearance))
+        if self._engine is not None:
+            self._push_world_cloud(self._engine)
+        else:
+            self.engine()
+
+    def _push_world_cloud(self, eng):
+        self._push_collision_model(eng)
+        eng.set_world_cloud(*self._world_cloud)
 
     def set_path_sweep(self, n_samples: int):
         """Samples per edge of generate_ik_path's lattice (0: no sweep, the default; at most 16).  While set, the path also avoids every edge
