@@ -192,6 +192,11 @@ SIGNATURES = {
     "ikf_plan_describe_for": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "ikf_set_gemm_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "ikf_rank_chunks": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
+    # m, d_poses, d_idx, n_mod, d_latent, n, clamp_to_limits, softflow_scale, d_q_out, stream
+    "ikf_generate_approx_tiled": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p],
+    ),
 }
 
 # ... every symbol include/ikflow_amd_rank.h declares (best-of-K ranking: not part of the boundary a binding of the reference needs)

@@ -602,17 +602,19 @@ ikf_status ikf::check_ready(ikf_model* m, const char* fn) {
   return IKF_OK;
 }
 
-// The frame of the three flow entries: the handle is ready, n is sane (0 rows: nothing to do), the entry's own pointers are there
-// (`null_args`: what is wrong with them, or null), then `body(ps, s)` on the handle's device inside the stream scope.
+// The frame of the flow entries: the handle is ready, n is sane (0 rows: nothing to do), the entry's own pointers are there
+// (`null_args`: what is wrong with them, or null), then `body(ps, s)` on the handle's device inside the stream scope.  `d_idx` / `n_mod`: the
+// pose source's list and modulus (batch form: null / n, single pose: null / 1, tiling: anything else, ikf_internal.h).
 template <class Body> static ikf_status flow_call(ikf_model* m, const char* fn, int64_t n, const char* null_args, const float* d_poses,
-                                                  int pose_broadcast, float softflow_scale, void* stream, Body body) {
+                                                  const int32_t* d_idx, int64_t n_mod, float softflow_scale, void* stream, Body body) {
   ikf_status st = check_ready(m, fn);
   if (st != IKF_OK) return st;
   if (n < 0) return fail(IKF_ERR_BAD_ARGUMENT, std::string(fn) + ": n must be >= 0");
+  if (n_mod < 1) return fail(IKF_ERR_BAD_ARGUMENT, std::string(fn) + ": n_mod must be >= 1");
   if (n == 0) return IKF_OK;
   if (null_args) return fail(IKF_ERR_NULL_POINTER, std::string(fn) + ": " + null_args);
   IKF_ON_DEVICE(m)
-  const PoseSource ps{d_poses, nullptr, pose_broadcast ? 1 : (long long)n, 7, softflow_scale};
+  const PoseSource ps{d_poses, d_idx, (long long)n_mod, 7, softflow_scale};
   hipStream_t s = static_cast<hipStream_t>(stream);
   StreamScope scope(m, s);
   IKF_HIP(scope.enter());
@@ -622,11 +624,22 @@ template <class Body> static ikf_status flow_call(ikf_model* m, const char* fn, 
   return IKF_OK;
 }
 
+// the modulus of the two pose sources the public entries build: one pose per row, or one pose for every row (n <= 0 is flow_call's to answer)
+static int64_t batch_mod(int pose_broadcast, int64_t n) { return (pose_broadcast || n < 1) ? 1 : n; }
+
 extern "C" ikf_status ikf_generate_approx(ikf_model* m, const float* d_poses, int pose_broadcast, const float* d_latent,
                                           int64_t n, int clamp_to_limits, float softflow_scale, float* d_q_out,
                                           void* stream) {
   const char* null_args = (!d_poses || !d_latent || !d_q_out) ? "null device pointer" : nullptr;
-  return flow_call(m, "ikf_generate_approx", n, null_args, d_poses, pose_broadcast, softflow_scale, stream,
+  return flow_call(m, "ikf_generate_approx", n, null_args, d_poses, nullptr, batch_mod(pose_broadcast, n), softflow_scale, stream,
+                   [&](const PoseSource& ps, hipStream_t s) { return run_flow_guarded(m, ps, d_latent, n, clamp_to_limits, d_q_out, s); });
+}
+
+// ikf_generate_approx under the tiling pose source of exact IK (run_exact) and of the candidate stage (flow_candidates): tests (ikflow_amd_debug.h)
+extern "C" ikf_status ikf_generate_approx_tiled(ikf_model* m, const float* d_poses, const int32_t* d_idx, int64_t n_mod, const float* d_latent,
+                                                int64_t n, int clamp_to_limits, float softflow_scale, float* d_q_out, void* stream) {
+  const char* null_args = (!d_poses || !d_latent || !d_q_out) ? "null device pointer" : nullptr;
+  return flow_call(m, "ikf_generate_approx_tiled", n, null_args, d_poses, d_idx, n_mod, softflow_scale, stream,
                    [&](const PoseSource& ps, hipStream_t s) { return run_flow_guarded(m, ps, d_latent, n, clamp_to_limits, d_q_out, s); });
 }
 
@@ -686,7 +699,7 @@ extern "C" ikf_status ikf_flow_forward(ikf_model* m, const float* d_x, int64_t n
                                        float softflow_scale, float* d_z_out, float* d_log_det_out, void* stream) {
   const char* null_args = (!d_x || !d_poses) ? "null device pointer"
                           : (!d_z_out && !d_log_det_out) ? "d_z_out and d_log_det_out are both null" : nullptr;
-  return flow_call(m, "ikf_flow_forward", n, null_args, d_poses, pose_broadcast, softflow_scale, stream,
+  return flow_call(m, "ikf_flow_forward", n, null_args, d_poses, nullptr, batch_mod(pose_broadcast, n), softflow_scale, stream,
                    [&](const PoseSource& ps, hipStream_t s) {
     if (m->d_ro_sub_fwd != nullptr) return run_forward_rowowner(m, ps, d_x, n, d_z_out, d_log_det_out, s);
     return for_each_chunk(m, 0, n, [&](long long r0, long long nr) { return run_forward_chunk_per_layer(m, ps, d_x, r0, nr, d_z_out, d_log_det_out, s); });
@@ -751,7 +764,7 @@ extern "C" ikf_status ikf_flow_inverse(ikf_model* m, const float* d_latent, int6
                                        float* d_log_det_out, void* stream) {
   const char* null_args = (!d_latent || !d_poses) ? "null device pointer"
                           : (!d_x_out && !d_q_out && !d_log_det_out) ? "d_x_out, d_q_out and d_log_det_out are all null" : nullptr;
-  return flow_call(m, "ikf_flow_inverse", n, null_args, d_poses, pose_broadcast, softflow_scale, stream,
+  return flow_call(m, "ikf_flow_inverse", n, null_args, d_poses, nullptr, batch_mod(pose_broadcast, n), softflow_scale, stream,
                    [&](const PoseSource& ps, hipStream_t s) {
     if (m->ro_stream != nullptr && m->d_ro_sub != nullptr)   // (the row-owner image exists: the released shape)
       return run_inverse_ld_rowowner(m, ps, d_latent, n, clamp_to_limits, d_x_out, d_q_out, d_log_det_out, s);

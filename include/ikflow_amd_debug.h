@@ -81,6 +81,10 @@ int ikf_rank_chunks(const ikf_model* m, int64_t n_poses, int k);
  *                    last partial round when nothing cheaper covers it) / always
  * Returns IKF_ERR_BAD_ARGUMENT if unknown. */
 ikf_status ikf_set_gemm_variant(ikf_model* m, int variant);
+/* ikf_generate_approx under the tiling pose source of exact IK and of the candidate stage (tests):
+ * pose of row r = d_poses + 7 * (d_idx ? d_idx[r % n_mod] : r % n_mod); d_idx: device int32 [n_mod], nullable; its values are the caller's to keep in range */
+ikf_status ikf_generate_approx_tiled(ikf_model* m, const float* d_poses, const int32_t* d_idx, int64_t n_mod, const float* d_latent,
+                                     int64_t n, int clamp_to_limits, float softflow_scale, float* d_q_out, void* stream);
 
 
 #ifdef __cplusplus

@@ -1,5 +1,6 @@
-"""What tests/test_flow_sample.py (GPU) and tests/test_flow_sample_inputs.py (CPU) share: the models, transforms, inputs and fp64 references
-of the sampling-pass tests, the guarded raw call and the switch that forces one launch form.
+"""What tests/test_flow_sample.py, tests/test_flow_sample_tiled.py (GPU) and tests/test_flow_sample_inputs.py,
+tests/test_flow_sample_tiled_inputs.py (CPU) share: the models, transforms, inputs and fp64 references of the sampling-pass tests, the guarded
+raw calls, the pose sources of the tiled tests and the switch that forces one launch form.
 
 Every reference a GPU test compares with comes from `reference(...)`, which only serves the keys listed in REFERENCE_SETS - and the CPU file
 holds every one of those to "the f32 torch oracle alone is within FLOW_TOL / 2 of the fp64 twin on every row".  A GPU test therefore cannot
@@ -175,11 +176,8 @@ def shared_solver(name, transform="plain", weights="A"):
 
 
 # ---- the guarded raw call ----------------------------------------------------------------------------------------------------------------
-def guarded_approx(eng, P, Z, clamp, soft=0.0, broadcast=False, stream=None, shift=0):
-    """ikf_generate_approx through the raw C-ABI into an int32 buffer of (GUARD + n + GUARD) x ndof words filled with SENTINEL (with `shift`
-    further words in front: shift = 1 makes the output pointer 4-byte aligned only); the pointer passed is that of row GUARD.  Both guard
-    bands must come back bit-unchanged, and no element of rows 0 .. n - 1 may still hold the sentinel - a NaN payload no kernel produces, so
-    a hit is an element nobody wrote.  Returns the n rows as float32."""
+def _guarded_rows(eng, Z, stream, shift, call):
+    """The frame of guarded_approx and guarded_tiled: `call(n, rows pointer, stream pointer)` is the raw C-ABI call and returns its status."""
     n, ndof = Z.shape[0], eng.layout.ndof
     front = shift + GUARD * ndof
     buf = torch.full((front + (n + GUARD) * ndof,), SENTINEL, dtype=torch.int32, device=Z.device)
@@ -187,8 +185,7 @@ def guarded_approx(eng, P, Z, clamp, soft=0.0, broadcast=False, stream=None, shi
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream(Z.device))   # (the fill above ran on the current stream)
     s = C.c_void_p((torch.cuda.current_stream(Z.device) if stream is None else stream).cuda_stream)
-    code = eng.lib.ikf_generate_approx(eng._h, P.data_ptr(), 1 if broadcast else 0, Z.data_ptr(), n, 1 if clamp else 0, float(soft),
-                                       rows.data_ptr(), s)
+    code = call(n, rows.data_ptr(), s)
     assert code == _lib.IKF_OK, _lib.last_error(eng.lib)
     torch.cuda.synchronize()
     before, unwritten, after = torch.stack([(buf[:front] != SENTINEL).sum(), (rows == SENTINEL).sum(),
@@ -197,6 +194,157 @@ def guarded_approx(eng, P, Z, clamp, soft=0.0, broadcast=False, stream=None, shi
     assert after == 0, f"n={n}: {after} words behind row n - 1 were written"
     assert unwritten == 0, f"n={n}: {unwritten} elements of rows 0 .. n - 1 were never written"
     return rows.view(torch.float32).view(n, ndof)
+
+
+def guarded_approx(eng, P, Z, clamp, soft=0.0, broadcast=False, stream=None, shift=0):
+    """ikf_generate_approx through the raw C-ABI into an int32 buffer of (GUARD + n + GUARD) x ndof words filled with SENTINEL (with `shift`
+    further words in front: shift = 1 makes the output pointer 4-byte aligned only); the pointer passed is that of row GUARD.  Both guard
+    bands must come back bit-unchanged, and no element of rows 0 .. n - 1 may still hold the sentinel - a NaN payload no kernel produces, so
+    a hit is an element nobody wrote.  Returns the n rows as float32."""
+    return _guarded_rows(eng, Z, stream, shift, lambda n, rows, s: eng.lib.ikf_generate_approx(
+        eng._h, P.data_ptr(), 1 if broadcast else 0, Z.data_ptr(), n, 1 if clamp else 0, float(soft), rows, s))
+
+
+def guarded_tiled(eng, P, idx, n_mod, Z, clamp, soft=0.0, stream=None):
+    """The twin of guarded_approx for ikf_generate_approx_tiled (include/ikflow_amd_debug.h): the pose of row r is P[idx[r % n_mod]], or
+    P[r % n_mod] without a list (idx: device int32 [n_mod], or None).  Same sentinel, same guard bands, same three assertions."""
+    assert idx is None or (idx.dtype == torch.int32 and idx.is_contiguous() and idx.device == Z.device)
+    return _guarded_rows(eng, Z, stream, 0, lambda n, rows, s: eng.lib.ikf_generate_approx_tiled(
+        eng._h, P.data_ptr(), None if idx is None else idx.data_ptr(), int(n_mod), Z.data_ptr(), n, 1 if clamp else 0, float(soft), rows, s))
+
+
+# ---- the tiling pose source (tests/test_flow_sample_tiled.py) ----------------------------------------------------------------------------------
+# The pose table is always the model's whole pool (device_inputs: POOL rows, at least n); a list points anywhere into it.
+LIST_SEED = 43
+LIST_KINDS = ("scatter", "compacted")
+
+
+@functools.lru_cache(maxsize=None)
+def pose_list(kind, n_mod, pool):
+    """The index list of a pose source, a function of (kind, n_mod, pool) only, int32 [n_mod], read-only; None for kind None.
+    "scatter": n_mod draws with replacement from range(pool), entry 0 forced to pool - 1 and (n_mod >= 2) the last entry to 0: not monotone,
+    both ends of the table, and with n_mod == 1 a single entry that is not 0.  "compacted": an ascending subset without repeats, the shape
+    launch_compact_invalid produces."""
+    if kind is None:
+        return None
+    rng = np.random.default_rng([LIST_SEED, LIST_KINDS.index(kind), n_mod, pool])
+    if kind == "scatter":
+        idx = rng.integers(0, pool, size=n_mod)
+        idx[0] = pool - 1
+        if n_mod >= 2:
+            idx[-1] = 0
+    else:
+        idx = np.sort(rng.choice(pool, size=n_mod, replace=False))
+    idx = idx.astype(np.int32)
+    idx.setflags(write=False)
+    return idx
+
+
+@functools.lru_cache(maxsize=None)
+def device_pose_list(kind, n_mod, pool):
+    idx = pose_list(kind, n_mod, pool)
+    return None if idx is None else torch.from_numpy(idx.copy()).to(DEV)
+
+
+def source_rows(n_mod, kind, pool, n):
+    """int64 [n]: the row of the pose table that row r of a call reads under the source (n_mod, kind)."""
+    pm = np.arange(n, dtype=np.int64) % n_mod
+    idx = pose_list(kind, n_mod, pool)
+    return pm if idx is None else idx.astype(np.int64)[pm]
+
+
+def gathered(P, idx, n_mod, n):
+    """The n pose rows P[idx[r % n_mod]] (P[r % n_mod] without a list), by integer indexing only: what the batch form is given."""
+    pm = torch.arange(n, device=P.device) % n_mod
+    return (P[pm] if idx is None else P[idx.long()[pm]]).contiguous()
+
+
+def SOURCES(n):
+    """[(n_mod, list kind)]: the pose sources a call of n rows is run under - n_mod in {1, 2, 3, 15, 16, 17, 61, n - 1, n} within [1, n], each
+    without a list, scattered and compacted, and one list longer than the call (n + 5 entries, only the first n read)."""
+    mods = sorted({m for m in (1, 2, 3, 15, 16, 17, 61, n - 1, n) if 1 <= m <= n})
+    return [(m, kind) for m in mods for kind in (None,) + LIST_KINDS] + [(n + 5, "scatter")]
+
+
+# (a) of tests/test_flow_sample_tiled.py: (forms, models, sizes, plan must contain) - R runs the per-layer forms with "perlayer" in front
+TILED_ROWOWNER_N = (1, 17, 4097)
+TILED_CLUSTER_N = (17, 129, 257, 513, 1025, 2048)      # every member count G = 32, 16, 8, 4, 2 (two sizes at G = 2)
+TILED_PERLAYER_N = (1, 17, 33, 129, 513, 2049)         # the 16-row head, the 32-row head and k_subnet_entry
+ROWOWNER_LAUNCH_ROWS = 1 << 24                          # rows of one row-owner launch (kMaxLaunchRows, api_flow.hip)
+PER_LAYER_CHUNK = 16384                                 # rows of the per-layer kernels' scratch up to width 1024 (chunk_cap, api_handle.hip)
+TILED_CHUNK_N = (16385,)                               # T: the last chunk of the per-layer chunk loop starts at a non-zero row0
+TILED_TILE_N = (33, 300)
+TILED_UNFUSED_N = (100, 700)
+TILED_F16X3_N = (257, 2049)
+TILED_TILE_FORMS = ("tile0", "tile1", "tile2", "tile3", "tile4", "tile6", "entry-off", "entry-forced", "rows16-off")
+# (b): the seam sizes and their sources
+TILED_SEAM_N = (600, 2304, 4096 + 200, 2 * 4096 + 2049)
+
+
+def seam_sources(n):
+    mods = [m for m in (1, 7, 1000, 4097, n - 1) if m < 4097 or n >= 4097]
+    out = [(m, kind) for m in mods for kind in (None, "scatter")]
+    return out + ([(4096, None)] if n == 4096 + 200 else [])   # row 4096 + j wraps to pose j
+
+
+# (c): per model the sizes whose rows are compared with fp64 (the largest n of every row of (a)'s table), under three sources each
+TILED_REF_N = {"R": (4097, 2048, 2049, 300), "R10": (4097,), "T": (2049, 16385, 300, 700), "T300": (2049,), "T1": (700,)}
+
+
+def ref_sources(n):
+    return [(17, "scatter"), (n - 1, None), (1, "scatter")]
+
+
+def _tiled_sets():
+    """{(model, n_mod, list kind): rows}: every tiled input a GPU test compares with the oracle (plain transform, weights A, softflow 0).  A list
+    is a function of (n_mod, POOL), so the rows of a smaller n under the same source are the leading rows of the largest."""
+    sets = {}
+    for name, sizes in TILED_REF_N.items():
+        for n in sizes:
+            for key in ref_sources(n):
+                sets[(name,) + key] = max(sets.get((name,) + key, 0), n)
+    return sets
+
+
+TILED_SETS = _tiled_sets()
+# (d): (poses m, candidates k) of the ikf_generate_ranked comparison - a call of k * m rows under (n_mod = m, no list); (e): the edge tests' call
+TILED_RANKED = ((1, 16), (5, 3), (65, 16), (257, 16))
+TILED_EDGE = (333, 61, "scatter")
+
+
+def tiled_cases():
+    """{(model, n, n_mod, list kind)}: every call the GPU tests of tests/test_flow_sample_tiled.py make."""
+    table = [(("R", "R10"), TILED_ROWOWNER_N), (("R",), TILED_CLUSTER_N), (("R", "T", "T300"), TILED_PERLAYER_N), (("T",), TILED_CHUNK_N),
+             (("T", "R"), TILED_TILE_N), (("T", "T1"), TILED_UNFUSED_N), (("T", "R"), TILED_F16X3_N)]
+    cases = {(name, n) + src for names, sizes in table for name in names for n in sizes for src in SOURCES(n)}
+    cases |= {("R", n) + src for n in TILED_SEAM_N for src in seam_sources(n)}
+    cases |= {(name, n) + src for name, sizes in TILED_REF_N.items() for n in sizes for src in ref_sources(n)}
+    cases |= {("R", k * m, m, None) for m, k in TILED_RANKED}
+    cases |= {(name,) + TILED_EDGE for name in ("R", "T")}
+    return cases
+
+
+def tiled_conditional(name, n_mod, kind, n, soft=0.0):
+    lay = model(name)[2]
+    c = inputs(name)[1].numpy().astype(np.float64)[source_rows(n_mod, kind, POOL[name], n)]
+    return np.concatenate([c, np.full((n, 1), soft)], 1) if lay.dim_cond == 8 else c
+
+
+@functools.lru_cache(maxsize=None)
+def reference_tiled(name, n_mod, kind):
+    """fp64 oracle on the gathered conditional, unclamped, [TILED_SETS[key] x ndof]: computed once, sliced by the tests, never changed."""
+    n = TILED_SETS[(name, n_mod, kind)]
+    robot, hp, lay, sd = model(name)
+    ref = fo.run_inference_f64(sd, lay, robot, inputs(name)[0][:n].numpy().astype(np.float64), tiled_conditional(name, n_mod, kind, n), False)
+    ref.setflags(write=False)
+    return ref
+
+
+def reference_tiled_f32(name, n_mod, kind):
+    n = TILED_SETS[(name, n_mod, kind)]
+    robot, hp, lay, sd = model(name)
+    cond = torch.from_numpy(tiled_conditional(name, n_mod, kind, n).astype(np.float32))
+    return fo.run_inference_torch(sd, lay, robot, inputs(name)[0][:n], cond, False).numpy()
 
 
 # ---- forcing a launch form ---------------------------------------------------------------------------------------------------------------

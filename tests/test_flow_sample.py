@@ -13,7 +13,8 @@ plans).  tests/test_gpu_parity.py compares their values with the oracle; what it
   5. reload on a live handle refreshes every weight image;
   6. pointers that are 4-byte aligned only, a non-default stream.
 Values: sample_helpers.reference (fp64, oracle.flow_oracle.run_inference_f64) on every row, FLOW_TOL = 1e-5 relative to max(1, |x|).  The inputs'
-own conditions are checked without a GPU in tests/test_flow_sample_inputs.py.  No test here uses the give-up hooks (188 / 191), and every
+own conditions are checked without a GPU in tests/test_flow_sample_inputs.py.  Every call here uses the batch or the single-pose source; the
+tiling pose source of exact and ranked IK (n_mod below the rows, an index list) has the sibling tests/test_flow_sample_tiled.py.  No test here uses the give-up hooks (188 / 191), and every
 test that runs a cluster form requires ikf_cluster_repairs unchanged: a repaired call must not pass for a cluster result."""
 import contextlib
 
