@@ -14,6 +14,8 @@
 // The K loop is the 3-stage / one-barrier-per-tile pipeline of k_gemm_lrelu_p3 (flow_kernels.hip).
 // (Generating the A operand of the first hidden contraction on the fly was measured and rejected: its ~110 VALU
 // instructions per wave per K tile did not stay in the MFMA shadow - 98 us against 65 us + a 5 us entry kernel.)
+// The per-element steps (clamped scale, inverse coupling, sigmoid, the FixedLinearTransform step, limit clamp, pose row) are flow_math.h's,
+// shared with every other flow form.
 #include <type_traits>
 
 #include "ikf_internal.h"
@@ -145,8 +147,8 @@ __device__ __forceinline__ void finish_pending_rows(const PendingCoupling& pc, c
     float v = pl.xv[it];
     if (pc.P != nullptr && d >= off && d < off + nl) {
       const int j = d - off;
-      const float s_cl = clamp * (0.636f * atanf(sums[r * ROWBUF + j]));
-      v = (v - sums[r * ROWBUF + nl + j]) * expf(-s_cl);
+      const float s_cl = coupling_scale(clamp, sums[r * ROWBUF + j]);
+      v = coupling_inv(v, sums[r * ROWBUF + nl + j], s_cl);
     }
     cat[r * ROWBUF + d] = v;
   }
@@ -198,10 +200,7 @@ __global__ __launch_bounds__(NT) void k_subnet_entry(EntryArgs e) {
     if (idx < ER * ROWBUF && uk >= e.n_x && uk < IN) {
       int gr = m0 + ur;
       gr = gr < M ? gr : M - 1;
-      const long long grow = e.row0 + gr;
-      // one pose per row (n_mod == rows) and the single-pose broadcast (n_mod == 1) skip the 64-bit modulo
-      const long long pm = grow < e.ps.n_mod ? grow : (e.ps.n_mod == 1 ? 0 : grow % e.ps.n_mod);
-      const long long pi = e.ps.idx ? (long long)e.ps.idx[pm] : pm;
+      const long long pi = pose_row(e.ps, e.row0 + gr);
       pose_v[it] = e.ps.poses[pi * e.ps.stride + (uk - e.n_x)];
     }
   }
@@ -656,10 +655,10 @@ __global__ __launch_bounds__(256) void k_flow_finalize(FinalizeArgs f) {
     float q = 0.f;
     for (int k = 0; k < D; ++k) {
       float xv = cat[r * ROWBUF + state_src(f.pend, k)];
-      if (f.sigmoid) xv = 1.0f / (1.0f + expf(-xv));  // InvertibleSigmoidFlipped rev (ikflow/model.py:124-127)
-      q = fmaf(xv - f.b_lin[k], f.M_inv[k * D + j], q);
+      if (f.sigmoid) xv = sigmoid_rev(xv);  // InvertibleSigmoidFlipped rev (ikflow/model.py:124-127)
+      q = linear_rev_step(xv, f.b_lin[k], f.M_inv[k * D + j], q);
     }
-    if (f.clamp_limits) q = fminf(fmaxf(q, f.lo[j]), f.hi[j]);
+    if (f.clamp_limits) q = clamp_limit(q, f.lo, f.hi, j);
     f.q_out[(size_t)(m0 + r) * f.ndof + j] = q;
   }
 }
@@ -1050,9 +1049,7 @@ __global__ __launch_bounds__(NH * KKS * 64) void k_entry_gemm_skinny(EntryArgs e
   if (t < R * ROWBUF && uk >= e.n_x && uk < n_in) {
     int gr = m0 + ur;
     gr = gr < M ? gr : M - 1;
-    const long long grow = e.row0 + gr;
-    const long long pm = grow < e.ps.n_mod ? grow : (e.ps.n_mod == 1 ? 0 : grow % e.ps.n_mod);
-    const long long pi = e.ps.idx ? (long long)e.ps.idx[pm] : pm;
+    const long long pi = pose_row(e.ps, e.row0 + gr);
     pose_v = e.ps.poses[pi * e.ps.stride + (uk - e.n_x)];
   }
   IKF_TSTAMP(0)
@@ -1460,8 +1457,8 @@ __device__ __forceinline__ void pending16_finish(const PendingCoupling& pc, cons
     float v = ps.xv;
     if (pc.P != nullptr && d >= off && d < off + nl) {
       const int j = d - off;
-      const float s_cl = clamp * (0.636f * atanf(sums[r * ROWBUF + j]));
-      v = (v - sums[r * ROWBUF + nl + j]) * expf(-s_cl);
+      const float s_cl = coupling_scale(clamp, sums[r * ROWBUF + j]);
+      v = coupling_inv(v, sums[r * ROWBUF + nl + j], s_cl);
     }
     cat[r * ROWBUF + d] = v;
   }
@@ -1554,9 +1551,7 @@ __device__ __forceinline__ bool entry_gemm16_body(const EntryArgs& e, const Fuse
   if (t < R * ROWBUF && uk >= e.n_x && uk < n_in) {
     int gr = m0 + ur;
     gr = gr < M ? gr : M - 1;
-    const long long grow = e.row0 + gr;
-    const long long pm = grow < e.ps.n_mod ? grow : (e.ps.n_mod == 1 ? 0 : grow % e.ps.n_mod);
-    const long long pi = e.ps.idx ? (long long)e.ps.idx[pm] : pm;
+    const long long pi = pose_row(e.ps, e.row0 + gr);
     pose_v = e.ps.poses[pi * e.ps.stride + (uk - e.n_x)];
   }
   if constexpr (XL) {  // everything above is independent of the sibling workgroups; their partial sums and the state come now

@@ -1,6 +1,7 @@
 // flow_fused_probes.inc - the in-launch hand-over forms of round 3, measured slower than the launch boundaries they replace (CHANGELOG.md round 3;
 // TailSync + 3.6 % at 4096 rows / + 7.4 % at 512; k_flow_chain16 0.422 against 0.365 ms at 128 rows).  Included by flow_fused.hip
 // only under -DIKF_PROBES (lib/libikflow_amd_probes.so), where tests/test_gpu_parity.py keeps them bit-identical to the product's forms.
+// (The pose row and, through finish_pending_rows / pending16_finish, the coupling are flow_math.h's, as in the product's forms.)
 #if IKF_PROBES_PART == 1
 // ---------------------------------------------------------------------------------------------------------------
 // The next subnet's entry phase in the tail of the launch that produced its pending coupling (TailSync, ikf_internal.h).
@@ -57,9 +58,7 @@ __device__ __forceinline__ void tail_next_entry(const EntryArgs& e, const TailSy
     if (idx < R * ROWBUF && uk >= e.n_x && uk < n_in) {
       int gr = m0 + ur;
       gr = gr < M ? gr : M - 1;
-      const long long grow = e.row0 + gr;
-      const long long pm = grow < e.ps.n_mod ? grow : (e.ps.n_mod == 1 ? 0 : grow % e.ps.n_mod);
-      const long long pi = e.ps.idx ? (long long)e.ps.idx[pm] : pm;
+      const long long pi = pose_row(e.ps, e.row0 + gr);
       pose_v[it] = e.ps.poses[pi * e.ps.stride + (uk - e.n_x)];
     }
   }

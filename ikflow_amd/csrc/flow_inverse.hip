@@ -4,6 +4,7 @@
 // and, after subnet 2, the block's PermuteRandom reversed.  Blocks run N-1 .. 0, subnet 1 before subnet 2 (GLOWCouplingBlock rev).  The tail
 // (k_inv_exit) applies the sigmoid of sigmoid_on_output graphs and FixedLinearTransform rev on all D columns.  Correct, not tuned.
 //   log|det dx/dz| = - sum of every coupling's clamped s  (+ sum log(v (1 - v)), v = sigmoid(state), on sigmoid graphs)  + log|det M_inv|
+// Per-element arithmetic: flow_math.h; the last-Linear prologue and the launcher's switch: last_linear_st / IKF_NOUT_DISPATCH (ikf_internal.h).
 #include "ikf_internal.h"
 
 namespace ikf {
@@ -17,41 +18,15 @@ __global__ __launch_bounds__(256) void k_last_layer_coupling_inv(const float* __
   const int lane = threadIdx.x & 63;
   const long long wave0 = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const long long nwaves = (long long)gridDim.x * (blockDim.x >> 6);
-  const int width = d.width, G = width >> 8;
+  const int width = d.width;
   const int D = d.D, L1 = d.L1;
   const int nl = ca.which == 1 ? d.L2 : L1;
 
   for (long long row = wave0; row < rows; row += nwaves) {
-    float a[OUT];
-#pragma unroll
-    for (int j = 0; j < OUT; ++j) a[j] = 0.f;
-    for (int g = 0; g < G; ++g) {
-      const float4 hv = reinterpret_cast<const float4*>(h + (size_t)row * width)[g * 64 + lane];
-#pragma unroll
-      for (int j = 0; j < OUT; ++j) {
-        const float4 w = reinterpret_cast<const float4*>(w_last + (size_t)j * width)[g * 64 + lane];
-        float sacc = a[j];
-        sacc = fmaf(hv.x, w.x, sacc);
-        sacc = fmaf(hv.y, w.y, sacc);
-        sacc = fmaf(hv.z, w.z, sacc);
-        sacc = fmaf(hv.w, w.w, sacc);
-        a[j] = sacc;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-      for (int j = 0; j < OUT; ++j) a[j] += __shfl_xor(a[j], off, 64);
-    // lane j < nl takes (s_j, t_j) = (a[j], a[nl + j]) + bias
-    float sv = 0.f, tv = 0.f;
-#pragma unroll
-    for (int j = 0; j < OUT; ++j) {
-      const float aj = a[j] + b_last[j];
-      if (j == lane) sv = aj;
-      if (j == lane + nl) tv = aj;
-    }
-    const float s_cl = lane < nl ? d.clamp * (0.636f * atanf(sv)) : 0.f;
-    const float e = expf(-s_cl);
+    float sv, tv;
+    last_linear_st<OUT>(w_last, b_last, h, row, width, lane, nl, sv, tv);
+    const float s_cl = lane < nl ? coupling_scale(d.clamp, sv) : 0.f;
+    const float e = coupling_inv_factor(s_cl);
     const bool on = lane < D;
     const float* src_row = (ca.which == 1 ? ca.x_in : ca.state) + (size_t)row * D;
     const float xv = on ? src_row[lane] : 0.f;
@@ -59,41 +34,23 @@ __global__ __launch_bounds__(256) void k_last_layer_coupling_inv(const float* __
     const bool mine = lane >= off && lane < off + nl;
     const int src = mine ? lane - off : 0;
     const float t_j = __shfl(tv, src, 64), e_j = __shfl(e, src, 64);
-    float out = mine ? (xv - t_j) * e_j : xv;
+    float out = mine ? coupling_inv_apply(xv, t_j, e_j) : xv;
     if (ca.which == 2) out = __shfl(out, on ? ca.perm_inv[lane] : 0, 64);   // PermuteRandom rev: out[d] = cat[perm_inv[d]]
-    float ls = s_cl;
+    float ls = coupling_inv_ld(s_cl);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) ls += __shfl_xor(ls, o, 64);
     if (on) ca.state[(size_t)row * D + lane] = out;
-    if (lane == 0) ca.ld[row] = ca.first ? -ls : ca.ld[row] - ls;
+    if (lane == 0) ca.ld[row] = ca.first ? ls : ca.ld[row] + ls;
   }
-}
-
-template <int OUT>
-static hipError_t launch_last_inv_g(const SubnetWeights& w, const FlowDims& d, const float* h_in, const InvCouplingArgs& ca, long long rows,
-                                    hipStream_t s) {
-  long long waves = (rows + 3) / 4;
-  if (waves < 1) waves = 1;
-  const unsigned grid = (unsigned)((waves + 3) / 4);
-  hipLaunchKernelGGL((k_last_layer_coupling_inv<OUT>), dim3(grid), dim3(256), 0, s, w.w_last, w.b_last, h_in, d, ca, rows);
-  return hipGetLastError();
 }
 
 hipError_t launch_last_layer_coupling_inv(const SubnetWeights& w, const FlowDims& d, const float* h_in, const InvCouplingArgs& ca,
                                           long long rows, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
   if (d.width % 256 != 0) return hipErrorInvalidValue;
-  switch (w.n_out) {
-    case 2: return launch_last_inv_g<2>(w, d, h_in, ca, rows, s);
-    case 4: return launch_last_inv_g<4>(w, d, h_in, ca, rows, s);
-    case 6: return launch_last_inv_g<6>(w, d, h_in, ca, rows, s);
-    case 8: return launch_last_inv_g<8>(w, d, h_in, ca, rows, s);
-    case 10: return launch_last_inv_g<10>(w, d, h_in, ca, rows, s);
-    case 12: return launch_last_inv_g<12>(w, d, h_in, ca, rows, s);
-    case 14: return launch_last_inv_g<14>(w, d, h_in, ca, rows, s);
-    case 16: return launch_last_inv_g<16>(w, d, h_in, ca, rows, s);
-    default: return hipErrorInvalidValue;
-  }
+  IKF_NOUT_DISPATCH(w.n_out, hipLaunchKernelGGL((k_last_layer_coupling_inv<OUT>), dim3(last_layer_grid(rows)), dim3(256), 0, s, w.w_last,
+                                               w.b_last, h_in, d, ca, rows))
+  return hipGetLastError();
 }
 
 // one wave per row, lane j = output column j (D <= 16)
@@ -107,19 +64,18 @@ __global__ __launch_bounds__(256) void k_inv_exit(InvExitArgs a, long long rows)
   float v = on ? a.state[(size_t)row * D + lane] : 0.f;
   float ldt = 0.f;
   if (a.sigmoid) {   // InvertibleSigmoidFlipped rev: v = sigmoid(x); log-det term log(v (1 - v)) = -|x| - 2 log1p(exp(-|x|)) (no cancellation)
-    const float ax = fabsf(v);
-    ldt = on ? -ax - 2.0f * log1pf(expf(-ax)) : 0.f;
-    v = 1.0f / (1.0f + expf(-v));
+    ldt = on ? sigmoid_rev_ld(v) : 0.f;
+    v = sigmoid_rev(v);
   }
   // FixedLinearTransform rev: (x - b).mm(M_inv), column jc
-  const float xm = on ? v - a.b_lin[jc] : 0.f;
+  const float xm = on ? linear_rev_in(v, a.b_lin[jc]) : 0.f;
   float q = 0.f;
-  for (int k = 0; k < D; ++k) q = fmaf(__shfl(xm, k, 64), a.M_inv[k * D + jc], q);
+  for (int k = 0; k < D; ++k) q = linear_step(__shfl(xm, k, 64), a.M_inv[k * D + jc], q);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) ldt += __shfl_xor(ldt, off, 64);
   if (on && a.x_out != nullptr) a.x_out[(size_t)row * D + lane] = q;
   if (lane < a.ndof && a.q_out != nullptr) {
-    if (a.clamp_limits) q = fminf(fmaxf(q, a.lo[lane]), a.hi[lane]);
+    if (a.clamp_limits) q = clamp_limit(q, a.lo, a.hi, lane);
     a.q_out[(size_t)row * a.ndof + lane] = q;
   }
   if (lane == 0 && a.ld_out != nullptr) a.ld_out[row] = a.log_det0 + (a.ld[row] + ldt);

@@ -11,6 +11,9 @@
 //                            [:, :ndof], clamp_to_joint_limits   (ikflow_solver.py:99-102)
 //
 // All arithmetic is fp32 (ikflow/config.py:8); the MFMA used is the exact-f32 one (bitwise an fmaf chain).
+// The per-element steps (clamped scale, coupling, sigmoid, the FixedLinearTransform step, limit clamp, pose row) are flow_math.h's, shared with
+// every other flow form; the last Linear of a row as a wave dot product (last_linear_st) and the launcher's switch over its output count
+// (IKF_NOUT_DISPATCH) are ikf_internal.h's, shared with k_last_layer_coupling_fwd / _inv.
 #include <type_traits>
 
 #include "ikf_internal.h"
@@ -48,10 +51,7 @@ __global__ __launch_bounds__(256) void k_first_layer(const float* __restrict__ w
     }
     for (long long r = r_begin; r < r_end; ++r) {
       // block-uniform addresses: the compiler turns these into scalar loads
-      const long long gr = row0 + r;
-      const long long pm = gr % ps.n_mod;
-      const long long pi = ps.idx ? (long long)ps.idx[pm] : pm;
-      const float* pose = ps.poses + pi * ps.stride;
+      const float* pose = ps.poses + pose_row(ps, row0 + r) * ps.stride;
       const float* xr = x_in + (size_t)r * D + x_off;
       float4 acc = b;
 #pragma unroll
@@ -534,44 +534,15 @@ __global__ __launch_bounds__(256) void k_last_layer_coupling(const float* __rest
   const long long wave0 = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const long long nwaves = (long long)gridDim.x * (blockDim.x >> 6);
   const int width = d.width;
-  const int G = width >> 8;  // 256 hidden units per pass of the wave (4 per lane)
-
   const int D = d.D, L1 = d.L1, L2 = d.L2;
   const int nl = (ca.which == 1) ? L2 : L1;  // number of (s,t) pairs this subnet emits
 
   for (long long row = wave0; row < rows; row += nwaves) {
-    float a[OUT];
-#pragma unroll
-    for (int j = 0; j < OUT; ++j) a[j] = 0.f;
-    for (int g = 0; g < G; ++g) {
-      const float4 hv = reinterpret_cast<const float4*>(h + (size_t)row * width)[g * 64 + lane];
-#pragma unroll
-      for (int j = 0; j < OUT; ++j) {
-        const float4 w = reinterpret_cast<const float4*>(w_last + (size_t)j * width)[g * 64 + lane];  // L2-resident
-        float sacc = a[j];
-        sacc = fmaf(hv.x, w.x, sacc);
-        sacc = fmaf(hv.y, w.y, sacc);
-        sacc = fmaf(hv.z, w.z, sacc);
-        sacc = fmaf(hv.w, w.w, sacc);
-        a[j] = sacc;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-      for (int j = 0; j < OUT; ++j) a[j] += __shfl_xor(a[j], off, 64);
-
-    // lane j < nl takes (s_j, t_j) = (a[j], a[nl + j]) + bias
-    float sv = 0.f, tv = 0.f;
-#pragma unroll
-    for (int j = 0; j < OUT; ++j) {
-      const float aj = a[j] + b_last[j];
-      if (j == lane) sv = aj;
-      if (j == lane + nl) tv = aj;
-    }
+    float sv, tv;
+    last_linear_st<OUT>(w_last, b_last, h, row, width, lane, nl, sv, tv);
     // FrEIA: s = clamp * (0.636 * atan(s));  y = (x - t) * exp(-s)
-    const float s_cl = d.clamp * (0.636f * atanf(sv));
-    const float e = expf(-s_cl);
+    const float s_cl = coupling_scale(d.clamp, sv);
+    const float e = coupling_inv_factor(s_cl);
 
     if (ca.which == 1) {
       float xv = 0.f;
@@ -581,14 +552,14 @@ __global__ __launch_bounds__(256) void k_last_layer_coupling(const float* __rest
       const float t_j = __shfl(tv, src, 64);
       const float e_j = __shfl(e, src, 64);
       float outv = xv;  // x1 is carried through unchanged
-      if (lane >= L1 && lane < D) outv = (xv - t_j) * e_j;
+      if (lane >= L1 && lane < D) outv = coupling_inv_apply(xv, t_j, e_j);
       if (lane < D) ca.x_out[(size_t)row * D + lane] = outv;
     } else {
       // state row = [x1 | y2]; y1 = (x1 - t2) * exp(-s2) on lanes < L1
       float xv = 0.f;
       if (lane < D) xv = ca.x_out[(size_t)row * D + lane];
       float cat = xv;
-      if (lane < L1) cat = (xv - tv) * e;
+      if (lane < L1) cat = coupling_inv_apply(xv, tv, e);
       // PermuteRandom rev: out[:, d] = cat[:, perm_inv[d]]
       const int src = (lane < D) ? ca.perm_inv[lane] : 0;
       const float v = __shfl(cat, src, 64);
@@ -596,13 +567,13 @@ __global__ __launch_bounds__(256) void k_last_layer_coupling(const float* __rest
         if (lane < D) ca.x_out[(size_t)row * D + lane] = v;
       } else {
         // FixedLinearTransform rev: (x - b).mm(M_inv); then [:, :ndof] and clamp_to_joint_limits
-        const float vs = ca.sigmoid ? 1.0f / (1.0f + expf(-v)) : v;  // InvertibleSigmoidFlipped rev
-        const float xm = (lane < D) ? vs - ca.b_lin[lane] : 0.f;
+        const float vs = ca.sigmoid ? sigmoid_rev(v) : v;  // InvertibleSigmoidFlipped rev
+        const float xm = (lane < D) ? linear_rev_in(vs, ca.b_lin[lane]) : 0.f;
         float q = 0.f;
         const int jcol = lane < D ? lane : 0;
-        for (int k = 0; k < D; ++k) q = fmaf(__shfl(xm, k, 64), ca.M_inv[k * D + jcol], q);
+        for (int k = 0; k < D; ++k) q = linear_step(__shfl(xm, k, 64), ca.M_inv[k * D + jcol], q);
         if (lane < d.ndof) {
-          if (ca.clamp_limits) q = fminf(fmaxf(q, ca.lo[lane]), ca.hi[lane]);
+          if (ca.clamp_limits) q = clamp_limit(q, ca.lo, ca.hi, lane);
           ca.q_out[(size_t)row * d.ndof + lane] = q;
         }
       }
@@ -610,31 +581,13 @@ __global__ __launch_bounds__(256) void k_last_layer_coupling(const float* __rest
   }
 }
 
-template <int OUT>
-static hipError_t launch_last_g(const SubnetWeights& w, const FlowDims& d, const float* h_in, const CouplingArgs& ca,
-                                long long rows, hipStream_t s) {
-  long long waves = (rows + 3) / 4;  // ~4 rows per wave
-  if (waves < 1) waves = 1;
-  const unsigned grid = (unsigned)((waves + 3) / 4);
-  hipLaunchKernelGGL((k_last_layer_coupling<OUT>), dim3(grid), dim3(256), 0, s, w.w_last, w.b_last, h_in, d, ca, rows);
-  return hipGetLastError();
-}
-
 hipError_t launch_last_layer_coupling(const SubnetWeights& w, const FlowDims& d, const float* h_in,
                                       const CouplingArgs& ca, long long rows, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
   if (d.width % 256 != 0) return hipErrorInvalidValue;
-  switch (w.n_out) {
-    case 2: return launch_last_g<2>(w, d, h_in, ca, rows, s);
-    case 4: return launch_last_g<4>(w, d, h_in, ca, rows, s);
-    case 6: return launch_last_g<6>(w, d, h_in, ca, rows, s);
-    case 8: return launch_last_g<8>(w, d, h_in, ca, rows, s);
-    case 10: return launch_last_g<10>(w, d, h_in, ca, rows, s);
-    case 12: return launch_last_g<12>(w, d, h_in, ca, rows, s);
-    case 14: return launch_last_g<14>(w, d, h_in, ca, rows, s);
-    case 16: return launch_last_g<16>(w, d, h_in, ca, rows, s);
-    default: return hipErrorInvalidValue;
-  }
+  IKF_NOUT_DISPATCH(w.n_out, hipLaunchKernelGGL((k_last_layer_coupling<OUT>), dim3(last_layer_grid(rows)), dim3(256), 0, s, w.w_last, w.b_last,
+                                               h_in, d, ca, rows))
+  return hipGetLastError();
 }
 
 }  // namespace ikf

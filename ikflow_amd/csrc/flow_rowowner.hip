@@ -20,6 +20,9 @@
 // Numerics: exact f32 fma chains on the matrix pipe like the per-layer kernels; another summation order (k ascending inside 16-k
 // groups permuted as k = 16 g + 4 j + c -> (c, j); even and odd groups in two chains that are added at the end), same tolerance
 // against the oracle.
+// The per-element steps (clamped scale, coupling in both directions with its log-det share, sigmoid / logit, the FixedLinearTransform step,
+// limit clamp, pose row) are flow_math.h's, shared with every other flow form; ro_new_state below is the one coupling of the row-owner, forward,
+// log-det and cluster kernels.
 #include "ikf_internal.h"
 
 #include <vector>
@@ -77,8 +80,10 @@ __device__ __forceinline__ void ro_barrier() {
 // FWD (k_flow_rowowner_fwd): the coupling runs forward, y = exp(s) x + t, and the permutation of the table sits on the subnet-1 entries
 // (PermuteRandom of the NEXT block, see rowowner_fwd_table); ld (nullable) accumulates the clamped s of the elements this thread rewrites.
 // Inverse pass with a log-determinant (k_flow_rowowner_ld): ld (nullable) accumulates MINUS the clamped s - the inverse map's share.
-template <bool FWD = false>
-__device__ __forceinline__ float ro_new_state(const float* __restrict__ xs_old, const float* __restrict__ red, const float* __restrict__ sm,
+// PARTS: `red` holds that many per-wave partial sums of the last Linear, to be added to the bias in sm; 0 (the cluster form): `red` is the
+// row tile's finished [row][RO_RS] sums, bias included.
+template <bool FWD = false, int PARTS = RO_WAVES>
+__device__ __forceinline__ float ro_new_state(const float* xs_old, const float* red, const float* sm,
                                               int row, int d, int L1, float clamp, float* ld = nullptr) {
   if (sm == nullptr) return xs_old[row * 16 + d];
   const int* smi = reinterpret_cast<const int*>(sm);
@@ -88,19 +93,25 @@ __device__ __forceinline__ float ro_new_state(const float* __restrict__ xs_old, 
   float v = xs_old[row * 16 + src];
   if (src >= off && src < off + nl) {
     const int j = src - off;
-    float s = sm[j], tt = sm[nl + j];
+    float s, tt;
+    if constexpr (PARTS != 0) {
+      s = sm[j], tt = sm[nl + j];
 #pragma unroll
-    for (int w = 0; w < RO_WAVES; ++w) {
-      s += red[w * (RO_ROWS * RO_RS) + row * RO_RS + j];
-      tt += red[w * (RO_ROWS * RO_RS) + row * RO_RS + nl + j];
-    }
-    const float s_cl = clamp * (0.636f * atanf(s));
-    if constexpr (FWD) {
-      v = expf(s_cl) * v + tt;
-      if (ld != nullptr) *ld += s_cl;
+      for (int w = 0; w < PARTS; ++w) {
+        s += red[w * (RO_ROWS * RO_RS) + row * RO_RS + j];
+        tt += red[w * (RO_ROWS * RO_RS) + row * RO_RS + nl + j];
+      }
     } else {
-      v = (v - tt) * expf(-s_cl);
-      if (ld != nullptr) *ld -= s_cl;
+      s = red[row * RO_RS + j];
+    }
+    const float s_cl = coupling_scale(clamp, s);
+    if constexpr (PARTS == 0) tt = red[row * RO_RS + nl + j];   // read after the scale, as this form always did: its instructions stay as they were
+    if constexpr (FWD) {
+      v = coupling_fwd(v, tt, s_cl);
+      if (ld != nullptr) *ld += coupling_fwd_ld(s_cl);
+    } else {
+      v = coupling_inv(v, tt, s_cl);
+      if (ld != nullptr) *ld += coupling_inv_ld(s_cl);
     }
   }
   return v;
@@ -172,11 +183,11 @@ __device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
       float v = 0.f;
       if (d < a.D) {
         const int src = f.perm0[d];
-        for (int k = 0; k < a.D; ++k) v = fmaf(a.x0[(size_t)gr * a.D + k], f.M[k * a.D + src], v);
+        for (int k = 0; k < a.D; ++k) v = linear_step(a.x0[(size_t)gr * a.D + k], f.M[k * a.D + src], v);
         v += a.b_lin[src];
         if (a.sigmoid) {
-          ld = -(logf(v) + log1pf(-v));
-          v = logf(v / (1.0f - v));
+          ld = logit_fwd_ld(v);
+          v = logit_fwd(v);
         }
       }
       xs[row * 16 + d] = v;
@@ -187,9 +198,7 @@ __device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
     const int row = (t - 256) >> 3, k = t & 7;
     int gr = m0 + row;
     gr = gr < a.M ? gr : a.M - 1;
-    const long long grow = a.row0 + gr;
-    const long long pm = grow < a.ps.n_mod ? grow : (a.ps.n_mod == 1 ? 0 : grow % a.ps.n_mod);
-    const long long pi = a.ps.idx ? (long long)a.ps.idx[pm] : pm;
+    const long long pi = pose_row(a.ps, a.row0 + gr);
     cond[row * 8 + k] = k < 7 ? a.ps.poses[pi * a.ps.stride + k] : a.ps.softflow;
   }
   for (int i = t; i < a.n_sub * RO_SMALL_WORDS; i += RO_WAVES * 64) small[i] = reinterpret_cast<const float*>(a.sub)[i];
@@ -341,17 +350,14 @@ __device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
         float q = 0.f;
         for (int k = 0; k < a.D; ++k) {
           float xv = x[k];
-          if (a.sigmoid) xv = 1.0f / (1.0f + expf(-xv));
-          q = fmaf(xv - a.b_lin[k], a.M_inv[k * a.D + j], q);
+          if (a.sigmoid) xv = sigmoid_rev(xv);
+          q = linear_rev_step(xv, a.b_lin[k], a.M_inv[k * a.D + j], q);
         }
-        if (a.sigmoid) {
-          const float ax = fabsf(x[j]);
-          ld += -ax - 2.0f * log1pf(expf(-ax));
-        }
+        if (a.sigmoid) ld += sigmoid_rev_ld(x[j]);
         if (live) {
           if (f.z_out != nullptr) f.z_out[(size_t)(m0 + row) * a.D + j] = q;
           if (a.q_out != nullptr && j < a.ndof) {
-            if (a.clamp_limits) q = fminf(fmaxf(q, a.lo[j]), a.hi[j]);
+            if (a.clamp_limits) q = clamp_limit(q, a.lo, a.hi, j);
             a.q_out[(size_t)(m0 + row) * a.ndof + j] = q;
           }
         }
@@ -371,10 +377,10 @@ __device__ __forceinline__ void ro_flow_body(const RoArgs& a, const RoFwd& f) {
       float q = 0.f;
       for (int k = 0; k < a.D; ++k) {
         float xv = x[k];
-        if (a.sigmoid) xv = 1.0f / (1.0f + expf(-xv));
-        q = fmaf(xv - a.b_lin[k], a.M_inv[k * a.D + j], q);
+        if (a.sigmoid) xv = sigmoid_rev(xv);
+        q = linear_rev_step(xv, a.b_lin[k], a.M_inv[k * a.D + j], q);
       }
-      if (a.clamp_limits) q = fminf(fmaxf(q, a.lo[j]), a.hi[j]);
+      if (a.clamp_limits) q = clamp_limit(q, a.lo, a.hi, j);
       a.q_out[(size_t)(m0 + row) * a.ndof + j] = q;
     }
   }
@@ -581,33 +587,17 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_cluster(RcArgs c) {
     const int row = (t - 256) >> 3, k = t & 7;
     int gr = m0 + row;
     gr = gr < a.M ? gr : a.M - 1;
-    const long long grow = a.row0 + gr;
-    const long long pm = grow < a.ps.n_mod ? grow : (a.ps.n_mod == 1 ? 0 : grow % a.ps.n_mod);
-    const long long pi = a.ps.idx ? (long long)a.ps.idx[pm] : pm;
+    const long long pi = pose_row(a.ps, a.row0 + gr);
     cond[row * 8 + k] = k < 7 ? a.ps.poses[pi * a.ps.stride + k] : a.ps.softflow;
   }
   for (int i = t; i < a.n_sub * RO_SMALL_WORDS; i += RO_WAVES * 64) small[i] = reinterpret_cast<const float*>(a.sub)[i];
   ro_barrier();
 
   // new state (threads 0..255) and the next subnet's input rows (threads 256..511) from the pending subnet's summed outputs in s_sum
-  auto new_state = [&](const float* sm, const float* xs_old, int row, int d) -> float {
-    if (sm == nullptr) return xs_old[row * 16 + d];
-    const int* smi = reinterpret_cast<const int*>(sm);
-    const int which = smi[32], nl = smi[35];
-    const int src = which == 2 ? smi[16 + d] : d;
-    const int off = which == 1 ? a.L1 : 0;
-    float v = xs_old[row * 16 + src];
-    if (src >= off && src < off + nl) {
-      const int jj = src - off;
-      const float s_cl = a.clamp * (0.636f * atanf(s_sum[row * RO_RS + jj]));
-      v = (v - s_sum[row * RO_RS + nl + jj]) * expf(-s_cl);
-    }
-    return v;
-  };
   auto advance = [&](const float* pend_sm, const float* nxt_sm, const float* xs_old, float* xs_new) {
     if (t < 256) {
       const int row = t >> 4, d = t & 15;
-      if (d < a.D) xs_new[row * 16 + d] = new_state(pend_sm, xs_old, row, d);
+      if (d < a.D) xs_new[row * 16 + d] = ro_new_state<false, 0>(xs_old, s_sum, pend_sm, row, d, a.L1, a.clamp);
     } else if (nxt_sm != nullptr) {
       const int row = (t - 256) >> 4, k = t & 15;
       const int* ni = reinterpret_cast<const int*>(nxt_sm);
@@ -617,7 +607,7 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_cluster(RcArgs c) {
       if (what >= 0) v = cond[row * 8 + what];
       else if (what == -1) v = 1.0f;
       else if (what == -100) v = cond[row * 8 + 7];
-      else if (what > -100) v = new_state(pend_sm, xs_old, row, x_off + (-2 - what));
+      else if (what > -100) v = ro_new_state<false, 0>(xs_old, s_sum, pend_sm, row, x_off + (-2 - what), a.L1, a.clamp);
       us[row * RO_US + k] = v;
     }
   };
@@ -992,10 +982,10 @@ __global__ __launch_bounds__(RO_WAVES * 64) void k_flow_cluster(RcArgs c) {
       float q = 0.f;
       for (int k = 0; k < a.D; ++k) {
         float xv = x[k];
-        if (a.sigmoid) xv = 1.0f / (1.0f + expf(-xv));
-        q = fmaf(xv - a.b_lin[k], a.M_inv[k * a.D + jj], q);
+        if (a.sigmoid) xv = sigmoid_rev(xv);
+        q = linear_rev_step(xv, a.b_lin[k], a.M_inv[k * a.D + jj], q);
       }
-      if (a.clamp_limits) q = fminf(fmaxf(q, a.lo[jj]), a.hi[jj]);
+      if (a.clamp_limits) q = clamp_limit(q, a.lo, a.hi, jj);
       a.q_out[(size_t)(m0 + row) * a.ndof + jj] = q;
     }
   }

@@ -5,6 +5,7 @@
 
 #include "../../include/ikflow_amd.h"
 #include "../../include/ikflow_amd_debug.h"
+#include "flow_math.h"  // PoseSource and the flow's per-element arithmetic (no HIP)
 #include "kin_math.h"
 #include "rank_math.h"
 #include "path_math.h"
@@ -30,19 +31,7 @@ struct SubnetWeights {
   int n_out;               // 2*L2 for subnet1, 2*L1 for subnet2
 };
 
-// ---- where the conditional (target pose) of a flow row comes from ------------------------------------------
-// pose of global row r = poses + stride * (idx ? idx[r % n_mod] : r % n_mod)
-//   batch form      : idx = null, n_mod = n,  stride = 7      (ikflow_solver.py:338)
-//   single-pose form: idx = null, n_mod = 1,  stride = 0..7   (ikflow_solver.py:333-336, y.expand)
-//   exact-IK tiling : idx = active-pose list, n_mod = n_active (ikflow_solver.py:182-186, cond.repeat((R,1)))
-struct PoseSource {
-  const float* poses;
-  const int* idx;
-  long long n_mod;
-  int stride;
-  float softflow;
-};
-
+// struct PoseSource (where the conditional of a flow row comes from) and pose_row(): flow_math.h
 struct FlowDims {
   int D, L1, L2, width, n_hidden, ndof, n_pose;  // n_pose = 7 real pose entries of the conditional
   float clamp, slope;
@@ -82,6 +71,59 @@ struct CouplingArgs {
 };
 hipError_t launch_last_layer_coupling(const SubnetWeights& w, const FlowDims& d, const float* h_in,
                                       const CouplingArgs& ca, long long rows, hipStream_t s);
+// What the three per-layer coupling kernels (k_last_layer_coupling here, _fwd in flow_forward.hip, _inv in flow_inverse.hip) share: one wave
+// per row, lane l owns k = 4 (64 g + l) .. +3 of the hidden row.  last_linear_st: the last Linear of row `row` as a wave dot product, reduced
+// over the wave; lane j < nl leaves with (sv, tv) = (s_j, t_j) = (a[j], a[nl + j]) + bias, every other lane with zeros where it has none.
+template <int OUT>
+__device__ __forceinline__ void last_linear_st(const float* w_last, const float* b_last, const float* h, long long row, int width, int lane, int nl, float& sv, float& tv) {
+  const int G = width >> 8;  // 256 hidden units per pass of the wave (4 per lane)
+  float a[OUT];
+#pragma unroll
+  for (int j = 0; j < OUT; ++j) a[j] = 0.f;
+  for (int g = 0; g < G; ++g) {
+    const float4 hv = reinterpret_cast<const float4*>(h + (size_t)row * width)[g * 64 + lane];
+#pragma unroll
+    for (int j = 0; j < OUT; ++j) {
+      const float4 w = reinterpret_cast<const float4*>(w_last + (size_t)j * width)[g * 64 + lane];  // L2-resident
+      float sacc = a[j];
+      sacc = fmaf(hv.x, w.x, sacc);
+      sacc = fmaf(hv.y, w.y, sacc);
+      sacc = fmaf(hv.z, w.z, sacc);
+      sacc = fmaf(hv.w, w.w, sacc);
+      a[j] = sacc;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+    for (int j = 0; j < OUT; ++j) a[j] += __shfl_xor(a[j], off, 64);
+  sv = 0.f;
+  tv = 0.f;
+#pragma unroll
+  for (int j = 0; j < OUT; ++j) {
+    const float aj = a[j] + b_last[j];
+    if (j == lane) sv = aj;
+    if (j == lane + nl) tv = aj;
+  }
+}
+// their launch: 256 threads, ~4 rows per wave; CALL sees the last Linear's output count as the constant OUT
+inline unsigned last_layer_grid(long long rows) {
+  long long waves = (rows + 3) / 4;
+  if (waves < 1) waves = 1;
+  return (unsigned)((waves + 3) / 4);
+}
+#define IKF_NOUT_DISPATCH(n_out, ...) \
+  switch (n_out) {                    \
+    case 2: { constexpr int OUT = 2; __VA_ARGS__; break; }   \
+    case 4: { constexpr int OUT = 4; __VA_ARGS__; break; }   \
+    case 6: { constexpr int OUT = 6; __VA_ARGS__; break; }   \
+    case 8: { constexpr int OUT = 8; __VA_ARGS__; break; }   \
+    case 10: { constexpr int OUT = 10; __VA_ARGS__; break; } \
+    case 12: { constexpr int OUT = 12; __VA_ARGS__; break; } \
+    case 14: { constexpr int OUT = 14; __VA_ARGS__; break; } \
+    case 16: { constexpr int OUT = 16; __VA_ARGS__; break; } \
+    default: return hipErrorInvalidValue;                    \
+  }
 int gemm_variant_count();
 const char* gemm_kernel_name();
 
