@@ -3,7 +3,10 @@ GPU tests (tests/test_exact_rounds.py) share.
 
 Nothing here is a new tolerance.  The band rule (band_pos = 1e-4 thr + 5e-7, band_rot = 1e-4 thr + 6e-7 / thr), the cap of 3 % on the band's share and
 |dq| <= 5e-6 + 8 x the twin's sensitivity are those of test_exact_ik_seeded_is_row_exact_against_the_oracle (tests/test_gpu_parity.py) and of
-refine_helpers.check_against_oracle, from which they are imported."""
+refine_helpers.check_against_oracle, from which they are imported.
+
+The last section serves tests/test_exact_flow.py and tests/test_exact_flow_inputs.py (ikf_generate_exact, the flow in): its cases, the raw call
+and the same schedule put together from ikf_generate_approx_tiled and ikf_generate_exact_seeded.  It has no criterion at all: bits."""
 import ctypes as C
 import functools
 import os
@@ -13,6 +16,8 @@ import torch
 
 import helpers as H
 import refine_helpers as RH
+import sample_helpers as sh
+from oracle import flow_oracle as fo
 from oracle import kinematics_oracle as ko
 
 BAND_CAP = RH.BAND_CAP
@@ -474,3 +479,142 @@ def late_byte_inputs():
     which, n, seed = LATE_BYTE
     q_true = truth(which, n, seed)
     return which, ko.forward_kinematics(orob_of(which), q_true), seed_tables(which, q_true, (1,), seed + 1, sigmas=(1.0, 3.0))[0][0].contiguous()
+
+
+# ---- the flow in (tests/test_exact_flow.py, tests/test_exact_flow_inputs.py) --------------------------------------------------------------------
+# ikf_generate_exact against its two parts, ikf_generate_approx_tiled followed by ikf_generate_exact_seeded.  Models, pools and weights are those of
+# sample_helpers; loose thresholds on random weights give all three rounds a strict sub-list (tests/test_exact_flow_inputs.py holds the counts).
+FLOW_RC = (1, 3, 10)
+FLOW_THR = (0.2, 1.0)
+FLOW_STEPS = 3
+LATENT_STRIDE = 37        # round i's latents start at row 37 i of the pool: no two rounds of a case share a row position
+# name -> (model, n, schedule, (pos_thr, rot_thr))
+FLOW_CASES = {f"{m}-{n}": (m, n, FLOW_RC, FLOW_THR) for m, n in (("R", 200), ("R10", 200), ("R8", 200), ("Rsig", 200), ("T", 200), ("R", 17),
+                                                                 ("R10", 17), ("R8", 17), ("Rsig", 17), ("T", 17), ("R", 1))}
+FLOW_CASES.update({
+    "R-450-tight": ("R", 450, FLOW_RC, (0.05, 0.3)),        # round 2 beyond one 4096-row row-owner chunk
+    "R-130-r2": ("R", 130, (2, 4, 40), FLOW_THR),           # R > 1 in round 0, and the same
+    "T-1800-tight": ("T", 1800, FLOW_RC, (0.02, 0.1)),      # round 2 beyond the 16384-row per-layer chunk
+    "T-200-all": ("T", 200, FLOW_RC, (10.0, 4.0)),          # everything solved in round 0
+    "T-200-none": ("T", 200, FLOW_RC, (1e-9, 1e-9)),        # nothing ever solved
+})
+FLOW_N200 = ("R-200", "R10-200", "R8-200", "Rsig-200", "T-200")
+
+
+def flow_latents(name, n, rc):
+    """Per round i the latents [n * rc[i] x D] on the CPU: rows 37 i .. of the model's pool (sample_helpers.inputs), or, where the pool is shorter
+    than that, helpers.latents(n * rc[i], D, 100 + i)."""
+    pool = sh.inputs(name)[0]
+    out = []
+    for i, R in enumerate(rc):
+        a, rows = LATENT_STRIDE * i, n * R
+        out.append(pool[a:a + rows] if a + rows <= pool.shape[0] else H.latents(rows, pool.shape[1], 100 + i))
+    return out
+
+
+def flow_case_inputs(case):
+    """(model name, poses [n x 7], latents per round, schedule, pos_thr, rot_thr) of one entry of FLOW_CASES, on the CPU."""
+    name, n, rc, (pos_thr, rot_thr) = FLOW_CASES[case]
+    return name, sh.inputs(name)[1][:n], flow_latents(name, n, rc), rc, pos_thr, rot_thr
+
+
+def oracle_flow_fn(name):
+    robot, hp, lay, sd = sh.model(name)
+    return lambda latent, poses_tiled: fo.generate_ik_solutions_torch(sd, lay, robot, poses_tiled, latent[: poses_tiled.shape[0]], clamp=True)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_schedule(case):
+    """The oracle's schedule on one entry of FLOW_CASES, round by round (the loop of ko.generate_exact_ik_solutions over ko.exact_round, fp64 LM,
+    which does not report its rounds) -> dict(active, rows, solved: one int per round run, sol, valid)."""
+    name, poses, lats, rc, pos_thr, rot_thr = flow_case_inputs(case)
+    robot = sh.model(name)[0]
+    flow_fn = oracle_flow_fn(name)
+    sol = torch.zeros(poses.shape[0], robot.ndof)
+    valid = torch.zeros(poses.shape[0], dtype=torch.bool)
+    active, rows, solved = [], [], []
+    for r, R in enumerate(rc):
+        idx = torch.nonzero(~valid)[:, 0]
+        if idx.numel() == 0:
+            break
+        new_sol, new_valid = ko.exact_round(robot, flow_fn(lats[r][: idx.numel() * R], poses[idx].repeat((R, 1))), poses[idx], R, pos_thr, rot_thr,
+                                            lm_dtype=torch.float64)
+        sol[idx], valid[idx] = new_sol, new_valid
+        active.append(int(idx.numel()))
+        rows.append(int(idx.numel()) * R)
+        solved.append(int(new_valid.sum()))
+    return dict(active=active, rows=rows, solved=solved, sol=sol, valid=valid)
+
+
+def run_flow_raw(eng, poses, rc, pos_thr, rot_thr, n_lm_steps, latents, sol=None, valid=None, stats_fill=None):
+    """The twin of run_seeded_raw for ikf_generate_exact: the _lib.LATENT_FN callback records (round, rows, dim) of every call and returns
+    latents[round].data_ptr() - device tensors made before the call, so the callback allocates nothing and enqueues nothing.
+    -> (sol, valid uint8, stats [rounds x 4] int64, calls)."""
+    from ikflow_amd import _lib
+
+    n, nr, ndof = int(poses.shape[0]), len(rc), eng.layout.ndof
+    assert poses.dtype == torch.float32 and poses.is_contiguous() and poses.device == eng.device
+    for lt in latents:
+        assert lt.dtype == torch.float32 and lt.is_contiguous() and lt.device == eng.device and lt.ndim == 2
+    if sol is None:
+        sol = torch.empty((n, ndof), dtype=torch.float32, device=eng.device)
+    if valid is None:
+        valid = torch.empty(n, dtype=torch.uint8, device=eng.device)
+    assert sol.is_contiguous() and valid.is_contiguous() and sol.dtype == torch.float32 and valid.dtype == torch.uint8
+    stream = eng._stream()
+    calls, err = [], []
+
+    def _cb(_user, rnd, rows, dim):
+        try:
+            calls.append((int(rnd), int(rows), int(dim)))
+            lt = latents[rnd]
+            assert lt.shape[1] == dim and lt.shape[0] >= rows, (rnd, tuple(lt.shape), int(rows), int(dim))   # never hand out fewer rows than asked for
+            return lt.data_ptr()
+        except BaseException as e:  # never let an exception cross the C boundary
+            err.append(e)
+            return 0
+
+    cb = _lib.LATENT_FN(_cb)
+    c_rc = (C.c_int32 * max(nr, 1))(*[int(r) for r in rc])
+    c_stats = (C.c_int64 * (4 * max(nr, 1)))()
+    if stats_fill is not None:
+        for i in range(4 * nr):
+            c_stats[i] = stats_fill
+    with torch.cuda.device(eng.device):
+        code = eng.lib.ikf_generate_exact(eng._h, poses.data_ptr(), n, c_rc, nr, int(n_lm_steps), float(pos_thr), float(rot_thr), cb, None,
+                                          sol.data_ptr(), valid.data_ptr(), c_stats, stream)
+        torch.cuda.current_stream(eng.device).synchronize()   # the latents outlive the kernels that read them
+    if err:
+        raise err[0]
+    eng._ck(code)
+    return sol, valid, np.array(list(c_stats), dtype=np.int64).reshape(max(nr, 1), 4)[:nr], calls
+
+
+def parts(eng, P, rc, pos_thr, rot_thr, n_lm_steps, latents):
+    """The schedule of ikf_generate_exact put together from the two entries that have strict suites of their own, with no re-entrant call on the
+    handle.  Round r's list is predicted on the host (arange(n), then the ascending poses with valid == 0 after the prefix rc[:r]); its seeds
+    are ikf_generate_approx_tiled (sample_helpers.guarded_tiled: clamp on, softflow 0) under the source (P, list_r, len(list_r)) on the first
+    len(list_r) * rc[r] rows of latents[r]; the prefix rc[:r + 1] is then run by run_seeded_raw on the seeds of rounds 0 .. r, and every list
+    the engine showed its callback must be the predicted one.  `latents`: per round a device tensor, or a callable (round, rows) -> tensor.
+    -> (sol, valid, stats [len(rc) x 4], lists) of the last prefix (stats rows of rounds never started are zero, as the one call leaves them)."""
+    n = int(P.shape[0])
+    lst = np.arange(n, dtype=np.int32)
+    predicted, seeds, out = [], [], None
+    for r in range(len(rc)):
+        if r > 0:
+            lst = np.flatnonzero(out[1].cpu().numpy() == 0).astype(np.int32)
+            if len(lst) == 0:
+                break
+        predicted.append(lst)
+        rows = len(lst) * int(rc[r])
+        Z = latents(r, rows) if callable(latents) else latents[r][:rows]
+        assert Z.shape[0] == rows and Z.is_contiguous(), (r, tuple(Z.shape), rows)
+        seeds.append(sh.guarded_tiled(eng, P, torch.from_numpy(lst).to(P.device), len(lst), Z, clamp=1))
+        out = run_seeded_raw(eng, P, rc[:r + 1], pos_thr, rot_thr, n_lm_steps, lambda rnd, idx, repeat: seeds[rnd])
+        assert len(out[3]) == len(predicted), (r, len(out[3]), len(predicted))
+        for j, (seen, want) in enumerate(zip(out[3], predicted)):
+            assert seen.dtype == np.int32 and np.array_equal(seen, want), (r, j, len(seen), len(want))
+    sol, valid, stats, lists = out
+    full = np.zeros((len(rc), 4), np.int64)
+    full[:len(stats)] = stats
+    return sol, valid, full, lists
