@@ -5,8 +5,11 @@ fp64 forward log-det evaluated at that x (tests/flow_logdet.py) AND against slog
 itself (so the formula is not trusted twice); consistency with generate_approx and flow_forward on the device; a row's result does not
 depend on its place in the batch, on the batch size or on which outputs are asked for.  Both device paths everywhere: the row-owner launch
 (k_flow_rowowner_ld: width padded to 1024, 3 hidden layers) and the per-layer kernels (flow_inverse.hip: every other shape).
-Tolerances: x 1e-5 relative to max(1, |x|) (the inverse-parity class), log-det 1e-4 absolute.  No gain-2.5 weights are used here, so the
-f32-noise clause of test_flow_forward._check is not needed."""
+Tolerances: x 1e-5 relative to max(1, |x|) (the inverse-parity class), log-det 1e-4 absolute, flat: the weights of this file have gains up
+to 2.0 on inputs where an f32 evaluation of the references stays inside them, so the f32-noise clause of test_flow_forward._check is not
+needed here.  Gain-2.5 weights (saturated couplings), every D, depth, padded width and forced contraction variant, the launch split at 2^24
+rows and random shapes are in tests/test_flow_inverse_shapes.py; the references and the guarded call both files use are in
+tests/flow_inverse_helpers.py."""
 import ctypes as C
 import math
 import os
@@ -16,7 +19,8 @@ import numpy as np
 import pytest
 import torch
 
-from flow_logdet import fd_logdet, forward_with_logdet
+from flow_inverse_helpers import DEV, FLOW_TOL, LD_TOL, _check, _cond, _edge_rows, _guarded_inverse, _refs, _rel
+from flow_logdet import fd_logdet
 from helpers import (O, _dense_fixed_transform, custom_model, fetch_arm_model, latents, panda_model, reachable_poses, released_model,
                      tiny_model)
 from ikflow_amd import _lib
@@ -24,11 +28,7 @@ from ikflow_amd.ikflow_solver import IKFlowSolver
 from oracle import flow_oracle as fo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-FLOW_TOL = 1e-5     # relative to max(1, |x|)
-LD_TOL = 1e-4       # absolute, log|det| of O(10)
 RT_TOL = 3e-5       # forward(inverse(z)) = z on the device: the round-trip bound of tests/test_flow_forward.py
-SENTINEL = 0x7FC0DEAD   # a NaN whose payload no kernel writes
 CHUNK = 16384
 LOG_2PI = math.log(2.0 * math.pi)
 
@@ -47,76 +47,11 @@ def _inputs(model, n, seed):
     return latents(n, lay.dim, seed + 1), poses
 
 
-def _cond(lay, poses, soft=0.0):
-    """The oracle's conditional: [pose] or [pose, softflow scale]."""
-    c = np.asarray(poses, dtype=np.float64)
-    if lay.dim_cond == 8:
-        c = np.concatenate([c, np.full((c.shape[0], 1), soft)], 1)
-    return c
-
-
-def _np(t):
-    return t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-
-
-def _refs(sd, lay, z, cond):
-    """fp64 (x [n x D] = output_rev, log|det dx/dz| [n] = minus the forward log-det at x)."""
-    x_ref = fo.flow_inverse_f64(sd, lay, np.asarray(_np(z), dtype=np.float64), cond)
-    return x_ref, -forward_with_logdet(sd, lay, x_ref, cond)[1]
-
-
-def _rel(a, ref):
-    return float((np.abs(_np(a) - ref) / np.maximum(1.0, np.abs(ref))).max())
-
-
 def _fd_agrees(a, fd, tol=1e-5):
     """A central difference whose +-h step crosses a LeakyReLU kink is off in that row: 99 % of the rows to tol, every row to 1e-3.
     tol 1e-5 for the fp64 formula, LD_TOL for the f32 kernel."""
     d = np.abs(a - fd)
     return float(np.mean(d <= tol)) >= 0.99 and float(d.max()) <= 1e-3
-
-
-def _check(tag, sd, lay, z, cond, x, ld, rows=None, refs=None):
-    """x (FLOW_TOL relative to max(1, |x|)) and log|det dx/dz| (LD_TOL absolute) against the fp64 references on `rows` (None: every row)."""
-    z, x, ld = _np(z), _np(x), _np(ld)
-    idx = np.arange(x.shape[0]) if rows is None else np.asarray(rows)
-    x_ref, ld_ref = refs if refs is not None else _refs(sd, lay, z[idx], cond[idx])
-    assert np.isfinite(x[idx]).all() and np.isfinite(ld[idx]).all(), tag
-    xerr, lerr = _rel(x[idx], x_ref), float(np.abs(ld[idx] - ld_ref).max())
-    line = (f"{tag}: {'every row' if rows is None else f'{len(idx)} sampled rows'} of {x.shape[0]}: max |dx| rel {xerr:.2e}, "
-            f"max |dlog_det| {lerr:.2e} (|log_det| up to {np.abs(ld_ref).max():.1f})")
-    print(line)
-    assert xerr <= FLOW_TOL and lerr <= LD_TOL, line
-    return xerr, lerr
-
-
-def _edge_rows(n, edges=(), k=256, seed=0):
-    """Row sample: first, last, both rows at every edge, k seeded random rows (sorted, unique)."""
-    s = {0, n - 1}
-    for e in edges:
-        s.update(r for r in (e - 1, e) if 0 <= r < n)
-    s.update(np.random.default_rng(seed).integers(0, n, size=min(k, n)).tolist())
-    return np.array(sorted(s))
-
-
-def _guarded_inverse(eng, Z, P, clamp=False, soft=0.0, broadcast=False, want=(True, True, True)):
-    """ikf_flow_inverse through the raw C-ABI into x / q / log_det buffers with 64 extra rows of a NaN sentinel behind each: the rows
-    past n - 1 - and a buffer whose pointer was not passed - must come back bit-unchanged.  Returns (x, q, log_det), None where not wanted."""
-    n, D = Z.shape
-    ndof = eng.layout.ndof
-    bufs = [torch.full((n + 64, D), SENTINEL, dtype=torch.int32, device=DEV), torch.full((n + 64, ndof), SENTINEL, dtype=torch.int32, device=DEV),
-            torch.full((n + 64,), SENTINEL, dtype=torch.int32, device=DEV)]
-    ptrs = [b.data_ptr() if w else None for b, w in zip(bufs, want)]
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    code = eng.lib.ikf_flow_inverse(eng._h, Z.data_ptr(), n, P.data_ptr(), 1 if broadcast else 0, soft, 1 if clamp else 0, ptrs[0], ptrs[1],
-                                    ptrs[2], stream)
-    assert code == _lib.IKF_OK, _lib.last_error()
-    torch.cuda.synchronize()
-    out = []
-    for b, w in zip(bufs, want):
-        assert bool((b[n if w else 0:] == SENTINEL).all()), f"n={n}: store past row n - 1, or into an output that was not asked for"
-        out.append(b[:n].view(torch.float32) if w else None)
-    return out
 
 
 # ---- 1. CPU: the symbol, its ctypes signature, the solver's methods ------------------------------------------------------------------
