@@ -278,6 +278,15 @@ REFINE_SIGNATURES = {
     ),
 }
 
+# ... every symbol include/ikflow_amd_exact_world.h declares (exact IK that obeys the world: collision-free solutions from the retry loop)
+EXACT_WORLD_SIGNATURES = {
+    # on, reject_self, self_min_clearance
+    "ikf_set_exact_collision": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float]),
+    "ikf_get_exact_collision": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    # h_rows[IKF_MAX_ROUNDS]
+    "ikf_exact_collision_rejected": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+}
+
 LIB_PATH = _build.LIB_PATH
 _libs = {}
 
@@ -301,7 +310,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -160,14 +160,14 @@ static ikf_status ensure_exact_poses(ikf_model* m, long long poses) {
   return IKF_OK;
 }
 ikf_status ikf::ensure_exact_rows(ikf_model* m, long long rows) {
-  if (rows <= m->exact_rows) return IKF_OK;
+  if (rows <= m->exact_rows) return exact_rule_rows(m, m->exact_rows);   // (nothing, unless the rule or a cloud was set since the rows were sized)
   m->ex_q.release();
   m->ex_row_valid.release();
   m->exact_rows = 0;
   IKF_HIP(m->ex_q.ensure(rows * m->dims.ndof));
   IKF_HIP(m->ex_row_valid.ensure(rows));
   m->exact_rows = rows;
-  return IKF_OK;
+  return exact_rule_rows(m, rows);   // (the exact collision rule's cloud clearances, while a cloud is set: api_exact_world.hip)
 }
 ikf_status ikf::ensure_exact(ikf_model* m, long long poses, long long rows) {
   ikf_status st = ensure_exact_poses(m, poses);

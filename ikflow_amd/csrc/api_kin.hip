@@ -134,6 +134,9 @@ static ikf_status run_exact(ikf_model* m, const float* d_target_poses, int64_t n
     max_repeat = repeat_counts[r] > max_repeat ? repeat_counts[r] : max_repeat;
   }
   if (h_stats) memset(h_stats, 0, sizeof(int64_t) * 4 * n_rounds);
+  bool rule = false;  // the exact collision rule has something to test against (api_exact_world.hip)
+  ikf_status st = n > 0 ? exact_rule_begin(m, who, &rule) : IKF_OK;
+  if (st != IKF_OK) return st;
   if (n == 0) return IKF_OK;
   if (!d_target_poses || !d_q_out || !d_valid_out) return fail(IKF_ERR_NULL_POINTER, who + ": null device pointer");
   if (n > 0x7fffffffLL / 64 || n * (long long)repeat_counts[0] > 0x7fffffffLL) return fail(IKF_ERR_BAD_ARGUMENT, who + ": n too large");
@@ -143,7 +146,7 @@ static ikf_status run_exact(ikf_model* m, const float* d_target_poses, int64_t n
   // rounds; a larger worst case - or whatever ikf_reserve_exact has already provided - is not allocated for: the call
   // starts with round 0's rows and each later round grows to its measured n_active * R if it has to.
   const long long worst_rows = n * (long long)max_repeat;
-  ikf_status st = ensure_exact(m, n, worst_rows <= m->exact_upfront_rows ? worst_rows : n * (long long)repeat_counts[0]);
+  st = ensure_exact(m, n, worst_rows <= m->exact_upfront_rows ? worst_rows : n * (long long)repeat_counts[0]);
   if (st != IKF_OK) return st;
   StreamScope scope(m, s);
   IKF_HIP(scope.enter());
@@ -179,9 +182,9 @@ static ikf_status run_exact(ikf_model* m, const float* d_target_poses, int64_t n
       st = run_flow_guarded(m, ps, d_latent, rows, /*clamp=*/1, m->ex_q, s);  // seeds (:188)
       if (st != IKF_OK) return st;
     }
-    // all LM iterations of the round in one launch + one selection (kin_kernels.hip: k_exact_lm_iters)
-    IKF_HIP(launch_exact_lm_iters(m->d_chain, ndof, d_target_poses, m->ex_pose_idx, (int)n_active, R, n_lm_steps, d_q_seed, m->ex_q,
-                                  m->ex_row_valid, m->ex_pose_first, pos_thr, rot_thr, m->lm_precision, s));
+    // all LM iterations of the round in one launch + one selection (kin_kernels.hip: k_exact_lm_iters; under the rule: api_exact_world.hip)
+    st = exact_round_lm(m, rule, r, d_target_poses, (int)n_active, R, n_lm_steps, d_q_seed, pos_thr, rot_thr, s);
+    if (st != IKF_OK) return st;
     IKF_HIP(launch_exact_select_first(ndof, m->ex_pose_idx, (int)n_active, R, m->ex_q, m->ex_row_valid, d_q_out, d_valid_out,
                                       r == 0 ? 1 : 0, s));
     if (h_stats) {

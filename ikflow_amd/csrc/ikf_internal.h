@@ -14,6 +14,7 @@
 #include "cloud_math.h"
 #include "sweep_math.h"
 #include "refine_math.h"
+#include "exact_world_math.h"
 #include "flow_plan.h"  // IKF_RO_ROWS, the planner and the cluster back-off (host arithmetic, no HIP)
 
 namespace ikf {
@@ -580,5 +581,30 @@ hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s);
 // pose of row r is r % n_poses; q_out may be q_in; steps_out / converged_out [k * n_poses], each nullable.  lm_precision as launch_lm_step.
 hipError_t launch_refine(const Chain* d_chain, int ndof, const float* poses, long long n_poses, int k, const float* q_in, float* q_out, int n_steps,
                          float pos_tol, float rot_tol, uint8_t* steps_out, uint8_t* converged_out, int lm_precision, hipStream_t s);
+
+// exact_world_kernels.hip - exact IK under the exact collision rule (include/ikflow_amd_exact_world.h; the arithmetic: exact_world_math.h).
+// launch_exact_lm_iters_clear: launch_exact_lm_iters without pose_first, plus the world and self rule on every row's candidate - a rejected row
+// stores row_valid_iter = 0 and is added to *rejected_rows.  launch_exact_mask_rows: the same for the rows whose cloud clearance is < cloud_min.
+struct ExactClearArgs {
+  const Chain* ch;
+  const CollisionModel* cm;
+  const WorldModel* world;    // null or n_obs == 0: no world rule
+  int n_obs, n_caps;
+  float world_min;
+  int reject_self;
+  float self_min;
+  const float* poses;
+  const int* pose_idx;
+  int n_active, repeat, n_steps;
+  const float* q_in;          // seeds; may be q
+  float* q;
+  uint8_t* row_valid_iter;
+  float pos_thr, rot_thr;
+  int lm_precision;
+  unsigned long long* rejected_rows;   // one device word
+};
+hipError_t launch_exact_lm_iters_clear(const ExactClearArgs& a, int ndof, hipStream_t s);
+hipError_t launch_exact_mask_rows(uint8_t* row_valid_iter, const float* cloud_clearance, float cloud_min, long long rows,
+                                  unsigned long long* rejected_rows, hipStream_t s);
 
 }  // namespace ikf

@@ -1,6 +1,6 @@
 // The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
 // reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
-// those units (and api_rank / api_path / api_diverse / api_world / api_cloud / api_sweep / api_refine) only; the kernel-launch interface is ikf_internal.h.
+// those units (and api_rank / api_path / api_diverse / api_world / api_cloud / api_sweep / api_refine / api_exact_world) only; the kernel-launch interface is ikf_internal.h.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -167,6 +167,13 @@ struct ikf_model {
   DeviceBuf<int> ex_block_scratch;  // [2 * compact_blocks(poses)] per-block counts / offsets of the ordered compaction
   DeviceBuf<int> ex_count;        // device
   PinnedBuf<int> h_count;         // pinned host
+  // exact collision rule (api_exact_world.hip): off by default; while on, a repeat whose candidate hits the world, the cloud or - reject_self -
+  // the robot itself does not count
+  int ex_rule_on = 0, ex_reject_self = 0;
+  float ex_self_min_clearance = 0.f;
+  DeviceBuf<float> ex_cloud_row;  // [rows] the round's rows' cloud clearances (sized with the row state while a cloud is set)
+  DeviceBuf<unsigned long long> ex_rejected;  // [IKF_MAX_ROUNDS] rows with a candidate that a rule rejected, per round of the last call
+  bool ex_rejected_live = false;  // the last exact call ran under the rule (else ikf_exact_collision_rejected reports zeros)
   // best-of-K ranking scratch (api_rank.hip): the flow's candidate rows and the K-chunks' partial lists
   int n_caps = 0;                 // capsules of d_collision (sizes the ranking kernel's LDS)
   DeviceBuf<float> rk_q;          // [rows][ndof]
@@ -327,5 +334,13 @@ ikf_status reserve_candidates(ikf_model* m, const char* who, const char* rule, i
 // launch of k_cloud_clearance on the handle's cloud - both outputs nullable, the caller holds the stream scope.
 ikf_status ensure_cloud_partials(ikf_model* m, long long rows);
 ikf_status run_cloud_clearance(ikf_model* m, const float* d_q, long long rows, float* d_clearance, uint8_t* d_colliding, hipStream_t s);
+// The exact collision rule (api_exact_world.hip).  exact_rule_begin: before a call enqueues anything - is there anything to test against
+// (*active), and is the collision model there that it needs.  exact_rule_rows: the rule's own per-row buffer for `rows` rows while the rule is on and
+// a cloud is set (ensure_exact_rows calls it).  exact_round_lm: a round's LM launch on the rows in ex_q - launch_exact_lm_iters as it was when !active,
+// else the launches of the rule; either way ex_row_valid is what launch_exact_select_first reads next.
+ikf_status exact_rule_begin(ikf_model* m, const std::string& who, bool* active);
+ikf_status exact_rule_rows(ikf_model* m, long long rows);
+ikf_status exact_round_lm(ikf_model* m, bool active, int round, const float* d_target_poses, int n_active, int repeat, int n_lm_steps,
+                          const float* d_q_seed, float pos_thr, float rot_thr, hipStream_t s);
 }  // namespace ikf
 #pragma GCC visibility pop

@@ -480,6 +480,28 @@ class Engine:
                 None if steps is None else steps.data_ptr(), None if conv is None else conv.data_ptr(), self._stream()))
         return (out, steps, conv.to(torch.bool)) if return_info else out
 
+    # -- exact IK that obeys the world (include/ikflow_amd_exact_world.h) ----------------------------------------
+    def set_exact_collision(self, on: bool = True, reject_self: bool = False, self_min_clearance: float = 0.0) -> None:
+        """The exact collision rule (off by default).  While on, a repeat of generate_exact / refine_exact whose candidate - its q at the first
+        LM iteration inside both thresholds - is closer to the world of set_world or the cloud of set_world_cloud than their min_clearance, or,
+        with reject_self, to the robot itself than self_min_clearance, does not count: the pose is solved by its earliest admissible repeat or
+        goes to the next retry round.  Not while calls on this engine are in flight on another stream."""
+        self._ck(self.lib.ikf_set_exact_collision(self._h, 1 if on else 0, 1 if reject_self else 0, float(self_min_clearance)))
+
+    def exact_collision(self) -> Tuple[bool, bool, float]:
+        """-> (on, reject_self, self_min_clearance) in force on this engine."""
+        on, rs, mc = C.c_int(0), C.c_int(0), C.c_float(0.0)
+        self._ck(self.lib.ikf_get_exact_collision(self._h, C.byref(on), C.byref(rs), C.byref(mc)))
+        return bool(on.value), bool(rs.value), float(mc.value)
+
+    def exact_collision_rejected(self) -> List[int]:
+        """Per retry round of this engine's last exact call: rows that had a candidate and were rejected (zeros for rounds that did not run and
+        for a call with the rule off or nothing to test against).  Waits for that call."""
+        rows = (C.c_int64 * _lib.IKF_MAX_ROUNDS)()
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_exact_collision_rejected(self._h, rows))
+        return [int(v) for v in rows]
+
     # -- best-of-K ranking (include/ikflow_amd_rank.h) -----------------------------------------------------
     @property
     def has_collision_model(self) -> bool:

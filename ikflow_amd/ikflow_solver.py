@@ -133,6 +133,7 @@ class IKFlowSolver:
         self._world_cloud = None  # (points [n x 3] host f32, point_radius, min_clearance) of set_world_cloud: likewise
         self._path_sweep = 0  # samples per lattice edge of set_path_sweep: likewise
         self._candidate_refine = (0, 0.0, 0.0)  # (n_steps, pos_tol, rot_tol) of set_candidate_refine: likewise
+        self._exact_collision = (False, False, 0.0)  # (enabled, reject_self_collisions, min_clearance) of set_exact_collision: likewise
         # tests / tools only: "probes" binds lib/libikflow_amd_probes.so (the product + the priced-and-rejected forms of rounds 2 - 3);
         # set before the first call
         self.library_flavour = ""
@@ -187,6 +188,8 @@ class IKFlowSolver:
                 eng.set_path_sweep(self._path_sweep)
             if self._candidate_refine[0]:
                 eng.set_candidate_refine(*self._candidate_refine)
+            if self._exact_collision[0]:   # (after the collision model, the world and the cloud)
+                self._push_exact_collision(eng)
             self._engine = eng
         return self._engine
 
@@ -276,6 +279,28 @@ class IKFlowSolver:
         self._candidate_refine = (n_steps, float(pos_tol), float(rot_tol)) if n_steps else (0, 0.0, 0.0)
         if self._engine is not None:
             self._engine.set_candidate_refine(*self._candidate_refine)
+
+    def set_exact_collision(self, reject_self_collisions: bool = False, min_clearance: float = 0.0, enabled: bool = True):
+        """Make generate_exact_ik_solutions obey the scene (off by default).  While enabled, a repeat whose solution - its configuration at the
+        first LM iteration inside both error thresholds - is closer to the world of set_world or the cloud of set_world_cloud than their
+        min_clearance, or, with reject_self_collisions, to the robot itself than min_clearance, does not count: the pose is solved by its
+        earliest clear repeat, or falls through to the next round's larger repeat count (include/ikflow_amd_exact_world.h).  With nothing to
+        test against - no world, no cloud, reject_self_collisions False - the call is the plain one bit for bit."""
+        assert isinstance(enabled, bool), f"enabled must be a bool, got {enabled!r}"
+        assert isinstance(reject_self_collisions, bool), f"reject_self_collisions must be a bool, got {reject_self_collisions!r}"
+        assert isinstance(min_clearance, (int, float)) and not isinstance(min_clearance, bool) and math.isfinite(min_clearance), (
+            f"min_clearance must be a finite number, got {min_clearance!r}")
+        assert not (enabled and reject_self_collisions) or self._robot.has_collision_model, (
+            "reject_self_collisions needs a collision model (Robot.set_collision_capsules)")
+        self._exact_collision = (True, reject_self_collisions, float(min_clearance)) if enabled else (False, False, 0.0)
+        if self._engine is not None:
+            self._push_exact_collision(self._engine)
+
+    def _push_exact_collision(self, eng):
+        enabled, reject_self, min_clearance = self._exact_collision
+        if enabled and reject_self:
+            self._push_collision_model(eng)
+        eng.set_exact_collision(enabled, reject_self, min_clearance)
 
     def path_collides(self, path: torch.Tensor, n_samples: int, reject_self: bool = False, min_clearance: float = 0.0) -> torch.Tensor:
         """The swept check of a joint-space path [T x ndof]: per edge path[t] -> path[t + 1], whether one of its n_samples interpolated
@@ -388,7 +413,8 @@ class IKFlowSolver:
         latents: Optional[Sequence[torch.Tensor]] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Same as generate_ik_solutions() but refines the flow's seeds with Levenberg-Marquardt
-        (ikflow_solver.py:345-411). Returns (solutions [n x ndof], valids [n] bool); unsolved rows are 0."""
+        (ikflow_solver.py:345-411). Returns (solutions [n x ndof], valids [n] bool); unsolved rows are 0.  Under set_exact_collision a
+        solution that collides with the scene (or the robot itself) does not count: its pose is retried like an unsolved one."""
         assert target_poses.shape[1] == 7, f"target_poses must be of shape [n x 7], got {target_poses.shape}"
         assert isinstance(repeat_counts, tuple), f"repeat_counts must be a tuple, got {type(repeat_counts)}"
         assert not return_detailed, "return_detailed is not currently supported for generate_exact_ik_solutions()"

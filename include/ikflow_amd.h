@@ -174,7 +174,7 @@ ikf_status ikf_pose_distance(const float* d_poses_a, const float* d_poses_b, int
 ikf_status ikf_limits_exceeded(const float* d_q, int64_t n, int n_cols, const float* h_lower, const float* h_upper,
                                uint8_t* d_exceeded_out, void* stream);
 
-/* -- exact IK: replaces generate_exact_ik_solutions + _generate_exact_ik_solutions (:119-247, :345-411) ----- */
+/* -- exact IK: replaces generate_exact_ik_solutions + _generate_exact_ik_solutions (:119-247, :345-411).  A repeat that collides can be made not to count: include/ikflow_amd_exact_world.h. -- */
 /* Callback that supplies the latent for retry round `round`: must fill (or return a pointer to) a device buffer of
  * [rows x D] fp32 laid out tile-major exactly as the reference draws it (`draw_latent(..., (n_tiled, D))`, :187).
  * The Python shim draws it with torch.randn on the device - the same generator call the reference makes. */

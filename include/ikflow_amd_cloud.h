@@ -22,7 +22,8 @@
  *
  * Not covered: the sweep - while a cloud is set, ikf_set_path_sweep and ikf_sweep_edges keep testing the primitives and the robot itself only
  * (path IK tests its NODES against the cloud; edges times samples against 10^4 .. 10^6 points need a broad phase); a closest (point, capsule)
- * pair; a device-side source of points; per-point radii; culling of any kind; the exact-IK retry loop.
+ * pair; a device-side source of points; per-point radii; culling of any kind.  Exact IK obeys the cloud only while the exact collision rule is
+ * on (include/ikflow_amd_exact_world.h).
  */
 #ifndef IKFLOW_AMD_CLOUD_H
 #define IKFLOW_AMD_CLOUD_H
