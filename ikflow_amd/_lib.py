@@ -22,6 +22,7 @@ IKF_WORLD_MAX_OBSTACLES = 64
 IKF_CLOUD_MAX_POINTS = 1 << 20
 IKF_SWEEP_MAX_SAMPLES = 16
 IKF_REFINE_MAX_STEPS = 16
+IKF_WORLD_TRACK_MAX_FRAMES = 1024
 IKF_OBSTACLE_SPHERE, IKF_OBSTACLE_CAPSULE, IKF_OBSTACLE_HALF_SPACE, IKF_OBSTACLE_BOX = 0, 1, 2, 3
 
 IKF_OK = 0
@@ -287,6 +288,19 @@ EXACT_WORLD_SIGNATURES = {
     "ikf_exact_collision_rejected": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
 }
 
+# ... every symbol include/ikflow_amd_track.h declares (a world that moves along a path: one frame of obstacles per waypoint of path IK)
+TRACK_SIGNATURES = {
+    # h_frames [F][n], n_frames, n_obstacles, min_clearance
+    "ikf_set_world_track": (C.c_int, [C.c_void_p, C.POINTER(ikf_obstacle), C.c_int, C.c_int, C.c_float]),
+    "ikf_world_track_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    # t, i, h_out [n]
+    "ikf_world_track_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(ikf_obstacle)]),
+    # q, T, k, clearance_out, obstacle_out, capsule_out, colliding_out, stream
+    "ikf_world_track_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # q, T, k, q_start, reject_self, self_min_clearance, edge_free_out, stream
+    "ikf_sweep_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+}
+
 LIB_PATH = _build.LIB_PATH
 _libs = {}
 
@@ -310,7 +324,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

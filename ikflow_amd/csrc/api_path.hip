@@ -14,8 +14,11 @@ static ikf_status ensure_path_mask(ikf_model* m, long long rows, int k) {
   IKF_HIP(m->pt_edge_free.ensure(rows * sweep_words(k)));
   return IKF_OK;
 }
-// A sweep is set (ikf_set_path_sweep) and there is something to test against: obstacles on the handle, or the call rejects self-collisions.
-static bool path_sweeps(const ikf_model* m, const ikf_path_options* opt) { return m->path_sweep > 0 && (m->world_n > 0 || opt->reject_collisions); }
+// A sweep is set (ikf_set_path_sweep) and there is something to test against: obstacles on the handle, a world track (include/ikflow_amd_track.h),
+// or the call rejects self-collisions.
+static bool path_sweeps(const ikf_model* m, const ikf_path_options* opt) {
+  return m->path_sweep > 0 && (m->world_n > 0 || m->track_F > 0 || opt->reject_collisions);
+}
 // the shared latent expanded to one row per candidate row
 static ikf_status ensure_path_latent(ikf_model* m, long long rows) {
   IKF_HIP(m->pt_latent.ensure(rows * m->dims.D));
@@ -37,6 +40,8 @@ static ikf_status run_path(ikf_model* m, const float* d_waypoints, int64_t T, in
   // Its one kept row per waypoint goes to d_path_out, which the lattice launch behind it overwrites in full.
   float* const node = d_node_cost_out ? d_node_cost_out : m->pt_node.p;
   ikf_status st = score_candidates(m, d_waypoints, T, k, d_q, nullptr, scoring_options(*opt), d_path_out, nullptr, nullptr, nullptr, node, s);
+  if (st != IKF_OK) return st;
+  st = track_mask_nodes(m, d_q, T, k, node, s);   // a world track: +inf in place where a row hits its waypoint's key frame; nothing without one
   if (st != IKF_OK) return st;
   PathArgs a{};
   a.q = d_q;
@@ -69,6 +74,7 @@ static ikf_status run_path(ikf_model* m, const float* d_waypoints, int64_t T, in
     w.k = k;
     w.max_joint_step = opt->max_joint_step;
     w.edge_free = m->pt_edge_free.p;
+    track_fill_sweep(m, &w);
     IKF_HIP(prof_mark(m, s));   // bracketed like the sequential stage (tools/sweep_timing.py)
     IKF_HIP(launch_sweep_edges(m->dims.ndof, w, s));
     IKF_HIP(prof_mark(m, s));
@@ -87,6 +93,8 @@ extern "C" ikf_status ikf_path_search(ikf_model* m, const float* d_waypoints, in
   bool nothing = false;
   ikf_status st = path_check(m, "ikf_path_search", T, k, opt, d_waypoints, d_q, d_path_out, d_index_out, d_cost_out, &nothing);
   if (st != IKF_OK || nothing) return st;
+  st = track_check_T(m, "ikf_path_search", T);
+  if (st != IKF_OK) return st;
   IKF_ON_DEVICE(m)
   st = ensure_path_scratch(m, T * (long long)k);
   if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, T * (long long)k, k);
@@ -108,6 +116,8 @@ extern "C" ikf_status ikf_generate_path(ikf_model* m, const float* d_waypoints, 
   bool nothing = false;
   st = path_check(m, "ikf_generate_path", T, k, opt, d_waypoints, d_latent, d_path_out, d_index_out, d_cost_out, &nothing);
   if (st != IKF_OK || nothing) return st;
+  st = track_check_T(m, "ikf_generate_path", T);
+  if (st != IKF_OK) return st;
   IKF_ON_DEVICE(m)
   const long long rows = T * (long long)k;
   st = ensure_rank_rows(m, rows);
@@ -139,5 +149,8 @@ extern "C" ikf_status ikf_reserve_path(ikf_model* m, int64_t max_waypoints, int 
   st = ensure_path_scratch(m, rows);
   if (st == IKF_OK && m->loaded) st = ensure_path_latent(m, rows);
   if (st == IKF_OK && m->path_sweep > 0) st = ensure_path_mask(m, rows, max_k);   // (a sweep set later sizes its mask at the first call)
+  if (st == IKF_OK && m->track_F > 0) {   // a world track set by now: the zero node costs of ikf_sweep_lattice (its fine table was sized when it was set)
+    IKF_HIP(m->tk_zero_node.ensure(rows));
+  }
   return st;
 }

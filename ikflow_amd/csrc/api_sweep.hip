@@ -6,6 +6,9 @@
 extern "C" ikf_status ikf_set_path_sweep(ikf_model* m, int n_samples) {
   if (!m) return fail(IKF_ERR_NULL_POINTER, "ikf_set_path_sweep: null model");
   if (n_samples < 0 || n_samples > IKF_SWEEP_MAX_SAMPLES) return fail(IKF_ERR_BAD_ARGUMENT, "ikf_set_path_sweep: n_samples must be in 0 .. 16");
+  // a world track's fine frames are those of the sweep (include/ikflow_amd_track.h): rebuilt first, and a refused blend keeps the old value
+  ikf_status st = track_rebuild(m, "ikf_set_path_sweep", n_samples);
+  if (st != IKF_OK) return st;
   m->path_sweep = n_samples;
   return IKF_OK;
 }

@@ -13,6 +13,7 @@
 #include "world_math.h"
 #include "cloud_math.h"
 #include "sweep_math.h"
+#include "track_math.h"
 #include "refine_math.h"
 #include "exact_world_math.h"
 #include "flow_plan.h"  // IKF_RO_ROWS, the planner and the cluster back-off (host arithmetic, no HIP)
@@ -574,8 +575,32 @@ struct SweepArgs {
   int T, k;
   float max_joint_step;
   uint64_t* edge_free;        // [T][k][sweep_words(k)]
+  // lattice source under a world track (track_math.h): null / 0 without one - then the kernel is the one without a track (TRACK = false)
+  const WorldObstacle* track; // [track_fine_frames(track_frames, n_samples)][n_track] the fine table, built for n_samples
+  int n_track, track_frames;  // obstacles per frame, key frames (T <= track_frames)
+  float track_min_clearance;
 };
 hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s);
+
+// track_kernels.hip - a world track's nodes (include/ikflow_amd_track.h): row r * T + t of q against key frame t, which is frame
+// t * frame_stride of `frames`.  Two sinks: node != null - node[row] = +inf in place where the clearance is < min_clearance (rows already
+// +inf are skipped), the four outputs are not written; node == null - the four outputs, each nullable.
+struct TrackArgs {
+  const Chain* ch;
+  const CollisionModel* cm;
+  const WorldObstacle* frames;  // [..][n_obs]
+  int n_obs, n_caps;
+  long long frame_stride;       // frames between two key frames (S + 1 of the sweep the table was built for)
+  float min_clearance;
+  const float* q;               // [k * T][ndof] tile-major
+  int T, k;
+  float* node;                  // [k * T], or null
+  float* clearance;             // [k * T], or null
+  int* obstacle;
+  int* capsule;
+  uint8_t* colliding;
+};
+hipError_t launch_track_clearance(int ndof, const TrackArgs& a, hipStream_t s);
 
 // refine_kernels.hip - refined candidates (include/ikflow_amd_refine.h; the arithmetic: refine_math.h).  q [k * n_poses][ndof] tile-major, the
 // pose of row r is r % n_poses; q_out may be q_in; steps_out / converged_out [k * n_poses], each nullable.  lm_precision as launch_lm_step.

@@ -187,6 +187,14 @@ struct ikf_model {
   // swept edges of path IK (api_sweep.hip, api_path.hip): samples per lattice edge (0: no sweep) and the sweep kernel's verdicts, a bit per edge
   int path_sweep = 0;
   DeviceBuf<uint64_t> pt_edge_free;  // [T][k][sweep_words(k)]
+  // world track (api_track.hip, api_path.hip): key frames as they were set (normalised, f32), the fine table under track_S samples per edge on
+  // the host and on the device, and the zero node costs ikf_sweep_lattice hands the sweep kernel.  track_F == 0: no track.
+  int track_F = 0, track_n = 0, track_S = 0;
+  float track_min_clearance = 0.f;
+  std::vector<WorldObstacle> track_keys;   // [track_F][track_n]
+  std::vector<WorldObstacle> track_fine;   // [track_fine_frames(track_F, track_S)][track_n]
+  DeviceBuf<WorldObstacle> d_track;        // the same on the device
+  DeviceBuf<float> tk_zero_node;           // [rows]
   // refined candidates (api_refine.hip, api_rank.hip): LM steps on the flow's candidate rows before they are scored (0: none) and their tolerances
   int refine_steps = 0;
   float refine_pos_tol = 0.f, refine_rot_tol = 0.f;
@@ -338,6 +346,14 @@ ikf_status run_cloud_clearance(ikf_model* m, const float* d_q, long long rows, f
 // (*active), and is the collision model there that it needs.  exact_rule_rows: the rule's own per-row buffer for `rows` rows while the rule is on and
 // a cloud is set (ensure_exact_rows calls it).  exact_round_lm: a round's LM launch on the rows in ex_q - launch_exact_lm_iters as it was when !active,
 // else the launches of the rule; either way ex_row_valid is what launch_exact_select_first reads next.
+// The world track (api_track.hip).  track_rebuild: the fine table of the handle's key frames under S samples per edge, host and device
+// (nothing without a track; ikf_set_path_sweep calls it BEFORE it takes S - a refused blend reports frame and obstacle and leaves the table as
+// it was).  track_check_T: T <= F while a track is set.  track_mask_nodes: the node sink of k_track_clearance on a path call's node costs
+// (nothing without a track).  track_fill_sweep: the track's fields of a lattice SweepArgs (nothing without a track).
+ikf_status track_rebuild(ikf_model* m, const std::string& who, int S);
+ikf_status track_check_T(const ikf_model* m, const std::string& who, int64_t T);
+ikf_status track_mask_nodes(ikf_model* m, const float* d_q, int64_t T, int k, float* d_node, hipStream_t s);
+void track_fill_sweep(const ikf_model* m, SweepArgs* a);
 ikf_status exact_rule_begin(ikf_model* m, const std::string& who, bool* active);
 ikf_status exact_rule_rows(ikf_model* m, long long rows);
 ikf_status exact_round_lm(ikf_model* m, bool active, int round, const float* d_target_poses, int n_active, int repeat, int n_lm_steps,

@@ -13,6 +13,12 @@
 // The geometry of k_world_clearance: 64-thread workgroups, the lane's capsule end points in LDS (one slice per lane, stride (6 n_caps) | 1: odd,
 // so the lanes' slices start in different banks), the obstacle table staged once per workgroup and read as a broadcast.  A workgroup walks
 // waves blockIdx.x, blockIdx.x + gridDim.x, ...  Samples in ascending order; a lane stops at its first blocked sample.
+//
+// TRACK (the lattice source under a world track, include/ikflow_amd_track.h; taken only while a track is set): the waypoint t of a wave is
+// wave-uniform, so the fine frame a sample reads is too.  Per sample the wave stages that frame's n_track records into LDS behind the static
+// table (the start edge's key frame 0 once), every lane reads it as a broadcast like the static table, the lanes that are still undecided test
+// the sample (track_sample_blocked, track_math.h), and the wave leaves the sample loop when every lane is decided.  TRACK = false is the kernel
+// as it was, instruction for instruction (profiles/sweep_kernel_resources.txt).
 #include "ikf_internal.h"
 
 namespace ikf {
@@ -20,9 +26,12 @@ namespace ikf {
 constexpr size_t kSweepMaxLds = sizeof(float) * ((size_t)IKF_WORLD_TABLE_WORDS + IKF_SWEEP_LANES * (size_t)(IKF_MAX_CAPSULES * 6 + 1));
 static_assert(kSweepMaxLds == 4096 + 37120, "obstacle table + one wave's capsule slices");
 static_assert(kSweepMaxLds <= 48 * 1024 && kSweepMaxLds <= 160 * 1024, "a sweep workgroup fits the default dynamic LDS and a CU");
+constexpr size_t kSweepTrackMaxLds = kSweepMaxLds + sizeof(float) * (size_t)IKF_WORLD_TABLE_WORDS;
+static_assert(kSweepTrackMaxLds == 4096 + 4096 + 37120, "obstacle table + one fine frame + one wave's capsule slices");
+static_assert(kSweepTrackMaxLds <= 48 * 1024, "a tracked sweep workgroup fits the dynamic LDS that needs no opt-in");
 constexpr long long kSweepMaxGrid = 1LL << 20;
 
-template <int NDOF>
+template <int NDOF, bool TRACK>
 __global__ __launch_bounds__(IKF_SWEEP_LANES) void k_sweep_edges(const SweepArgs a) {
   extern __shared__ float sweep_lds[];   // [n_obs x 16] obstacle table, then [64][cap_stride] capsule end points
   const int lane = threadIdx.x;
@@ -31,7 +40,9 @@ __global__ __launch_bounds__(IKF_SWEEP_LANES) void k_sweep_edges(const SweepArgs
   const float* const src = n_obs > 0 ? reinterpret_cast<const float*>(a.world->obs) : nullptr;
   for (int i = lane; i < n_obs * IKF_WORLD_OBSTACLE_WORDS; i += IKF_SWEEP_LANES) OBS[i] = src[i];
   __syncthreads();
-  float* const w = sweep_lds + n_obs * IKF_WORLD_OBSTACLE_WORDS + lane * ((a.n_caps * 6) | 1);
+  const int n_track = TRACK ? a.n_track : 0;
+  float* const FRAME = sweep_lds + n_obs * IKF_WORLD_OBSTACLE_WORDS;   // TRACK: [n_track x 16] the fine frame of the sample in hand
+  float* const w = FRAME + n_track * IKF_WORLD_OBSTACLE_WORDS + lane * ((a.n_caps * 6) | 1);
   const bool lattice = a.lattice != 0;
   const long long T = a.T;
   const int k = a.k;
@@ -72,7 +83,29 @@ __global__ __launch_bounds__(IKF_SWEEP_LANES) void k_sweep_edges(const SweepArgs
       load_q<NDOF>(a.qb, i, eb);
     }
     int first = -1;
-    if (active)
+    if constexpr (TRACK) {
+      long long t;
+      int r, word;
+      sweep_wave_role(wave, k, &t, &r, &word);
+      const int S = a.n_samples;
+      bool undecided = active;
+      for (int i = 1; i <= S; ++i) {
+        if (__ballot(undecided) == 0ULL) break;   // wave-uniform: the barriers below are reached by all 64 lanes or by none
+        if (i == 1 || t > 0) {
+          const float* const fsrc = reinterpret_cast<const float*>(a.track + track_sample_frame(t, i, S) * n_track);
+          __syncthreads();   // (the previous sample's readers are done with FRAME)
+          for (int x = lane; x < n_track * IKF_WORLD_OBSTACLE_WORDS; x += IKF_SWEEP_LANES) FRAME[x] = fsrc[x];
+          __syncthreads();
+        }
+        if (undecided && track_sample_blocked<NDOF>(a.ch, a.cm, reinterpret_cast<const WorldObstacle*>(OBS), n_obs, a.world_min_clearance,
+                                                    a.reject_self != 0, a.self_min_clearance, reinterpret_cast<const WorldObstacle*>(FRAME),
+                                                    n_track, a.track_min_clearance, ea, eb, i, S, w)) {
+          first = i - 1;
+          undecided = false;
+        }
+      }
+      __syncthreads();   // (the next wave of this workgroup restages FRAME)
+    } else if (active)
       first = sweep_edge<NDOF>(a.ch, a.cm, reinterpret_cast<const WorldObstacle*>(OBS), n_obs, a.world_min_clearance, a.reject_self != 0,
                                a.self_min_clearance, ea, eb, a.n_samples, w);
     if (lattice) {
@@ -98,9 +131,16 @@ hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s) {
     if (!a.qa || !a.qb || (!a.blocked_out && !a.first_out)) return hipErrorInvalidValue;
     waves = sweep_pair_waves(a.n);
   }
-  const size_t lds = sizeof(float) * ((size_t)a.n_obs * IKF_WORLD_OBSTACLE_WORDS + IKF_SWEEP_LANES * (size_t)((a.n_caps * 6) | 1));
+  const bool track = a.lattice && a.track != nullptr && a.n_track > 0;
+  if (track && (a.n_track > IKF_WORLD_MAX_OBSTACLES || a.track_frames < 1 || a.T > a.track_frames)) return hipErrorInvalidValue;
+  const size_t lds = sizeof(float) * (((size_t)a.n_obs + (track ? a.n_track : 0)) * IKF_WORLD_OBSTACLE_WORDS +
+                                      IKF_SWEEP_LANES * (size_t)((a.n_caps * 6) | 1));
   const unsigned grid = (unsigned)(waves < kSweepMaxGrid ? waves : kSweepMaxGrid);
-  IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
+  if (track) {
+    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND, true>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
+  } else {
+    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND, false>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
+  }
   return hipGetLastError();
 }
 

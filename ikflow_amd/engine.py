@@ -447,6 +447,99 @@ class Engine:
                                               float(min_clearance), blocked.data_ptr(), first.data_ptr(), self._stream()))
         return blocked.to(torch.bool), first
 
+    # -- world track (include/ikflow_amd_track.h) ----------------------------------------------------------------
+    @staticmethod
+    def _obstacle_array(obstacles):
+        arr = (_lib.ikf_obstacle * max(len(obstacles), 1))()
+        for o, (kind, a, b, quat, radius) in zip(arr, obstacles):
+            o.kind, o.radius = int(kind), float(radius)
+            for k in range(3):
+                o.a[k], o.b[k] = float(a[k]), float(b[k])
+            for k in range(4):
+                o.quat[k] = float(quat[k])
+        return arr
+
+    def set_world_track(self, frames, min_clearance: float = 0.0) -> None:
+        """frames: a sequence of F ikflow_amd.world.World (or lists of (kind, a[3], b[3], quat[4], radius)), one per waypoint, each the same n
+        obstacles with the same kinds (an empty sequence clears).  While a track is set, path_search / generate_path also drop candidate r of
+        waypoint t when its world clearance against frame t is below min_clearance, and - under set_path_sweep - block an edge whose samples come
+        closer than that to the frames interpolated between the two waypoints'.  Beside set_world and set_world_cloud, not instead of them.  Not
+        while calls on this engine are in flight on another stream."""
+        frames = [list(getattr(f, "obstacles", f)) for f in frames]
+        if len(frames) > _lib.IKF_WORLD_TRACK_MAX_FRAMES:
+            raise EngineError(f"a world track holds at most {_lib.IKF_WORLD_TRACK_MAX_FRAMES} frames, got {len(frames)}")
+        n = len(frames[0]) if frames else 0
+        for t, f in enumerate(frames):
+            if len(f) != n:
+                raise EngineError(f"frame {t} holds {len(f)} obstacles, frame 0 holds {n}: every frame of a world track holds the same obstacles")
+        if n > _lib.IKF_WORLD_MAX_OBSTACLES:
+            raise EngineError(f"a frame holds at most {_lib.IKF_WORLD_MAX_OBSTACLES} obstacles, got {n}")
+        arr = self._obstacle_array([o for f in frames for o in f])
+        self._ck(self.lib.ikf_set_world_track(self._h, arr, len(frames), n, float(min_clearance)))
+
+    def clear_world_track(self) -> None:
+        self._ck(self.lib.ikf_set_world_track(self._h, None, 0, 0, 0.0))
+
+    @property
+    def world_track_size(self) -> Tuple[int, int]:
+        """(key frames, obstacles per frame); (0, 0) without a track."""
+        f, n = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.ikf_world_track_size(self._h, C.byref(f), C.byref(n)))
+        return int(f.value), int(n.value)
+
+    def world_track_frame(self, t: int, i: int = 0):
+        """The f32 records the device reads for fine frame i (0 .. path_sweep; 0: the key frame itself) after key frame t, as a World."""
+        from ikflow_amd.world import World
+
+        n = self.world_track_size[1]
+        arr = (_lib.ikf_obstacle * max(n, 1))()
+        self._ck(self.lib.ikf_world_track_frame(self._h, int(t), int(i), arr))
+        w = World()
+        for o in arr[:n]:
+            w._add(int(o.kind), tuple(o.a), tuple(o.b), tuple(o.quat), float(o.radius))
+        return w
+
+    def world_track_clearance(self, q: torch.Tensor, T: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """q [k * T x ndof] tile-major, row r * T + t against key frame t of the track -> what world_clearance returns, colliding against the
+        track's min_clearance."""
+        q = self._q(q)
+        assert q.shape[0] == int(k) * int(T), f"q must be [{k * T} x {self.layout.ndof}], got {tuple(q.shape)}"
+        n = q.shape[0]
+        dist = torch.empty(n, dtype=torch.float32, device=self.device)
+        obstacle = torch.empty(n, dtype=torch.int32, device=self.device)
+        capsule = torch.empty(n, dtype=torch.int32, device=self.device)
+        col = torch.empty(n, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_world_track_clearance(self._h, q.data_ptr(), int(T), int(k), dist.data_ptr(), obstacle.data_ptr(), capsule.data_ptr(),
+                                                        col.data_ptr(), self._stream()))
+        return dist, obstacle, capsule, col.to(torch.bool)
+
+    def sweep_lattice(self, q: torch.Tensor, T: int, k: int, q_start: Optional[torch.Tensor] = None, reject_self: bool = False,
+                      min_clearance: float = 0.0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """The edge mask a path call builds from these rows (q [k * T x ndof] tile-major) under the engine's sweep, world and track and -
+        reject_self - the robot itself with min_clearance, nothing pruned -> (edge_free [T][k][k] bool: [t][r][j] the edge from candidate j of
+        waypoint t - 1 to candidate r of waypoint t, row 0 all True; start_free [k] bool for q_start -> q[0][r], None without q_start)."""
+        q = self._q(q)
+        T, k = int(T), int(k)
+        assert q.shape[0] == k * T, f"q must be [{k * T} x {self.layout.ndof}], got {tuple(q.shape)}"
+        if q_start is not None:
+            q_start = self._on_device(q_start, "q_start")
+            assert q_start.shape == (self.layout.ndof,), f"q_start must be [{self.layout.ndof}], got {tuple(q_start.shape)}"
+        words = (k + 63) // 64
+        mask = torch.zeros((T, k, words), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_sweep_lattice(self._h, q.data_ptr(), T, k, None if q_start is None else q_start.data_ptr(), 1 if reject_self else 0,
+                                                float(min_clearance), mask.data_ptr(), self._stream()))
+        shifts = torch.arange(64, dtype=torch.int64, device=self.device)
+        bits = ((mask[..., None] >> shifts) & 1).to(torch.bool).reshape(T, k, words * 64)
+        edge_free = bits[:, :, :k].clone()
+        start_free = None
+        if T > 0:
+            if q_start is not None:
+                start_free = bits[0, :, 0].clone()
+            edge_free[0] = True
+        return edge_free, start_free
+
     # -- refined candidates (include/ikflow_amd_refine.h) ------------------------------------------------------
     def set_candidate_refine(self, n_steps: int, pos_tol: float = 0.0, rot_tol: float = 0.0) -> None:
         """LM steps on every candidate row of generate_ranked / generate_diverse / generate_path, between the flow and the scoring (0: none, the

@@ -132,6 +132,7 @@ class IKFlowSolver:
         self._world = None   # (World, min_clearance) of set_world: re-applied to every engine this solver creates
         self._world_cloud = None  # (points [n x 3] host f32, point_radius, min_clearance) of set_world_cloud: likewise
         self._path_sweep = 0  # samples per lattice edge of set_path_sweep: likewise
+        self._world_track = None  # (worlds, min_clearance) of set_world_track: likewise (pushed after the collision model, the world and the sweep)
         self._candidate_refine = (0, 0.0, 0.0)  # (n_steps, pos_tol, rot_tol) of set_candidate_refine: likewise
         self._exact_collision = (False, False, 0.0)  # (enabled, reject_self_collisions, min_clearance) of set_exact_collision: likewise
         # tests / tools only: "probes" binds lib/libikflow_amd_probes.so (the product + the priced-and-rejected forms of rounds 2 - 3);
@@ -186,6 +187,8 @@ class IKFlowSolver:
                 self._push_world_cloud(eng)
             if self._path_sweep:
                 eng.set_path_sweep(self._path_sweep)
+            if self._world_track is not None:
+                self._push_world_track(eng)
             if self._candidate_refine[0]:
                 eng.set_candidate_refine(*self._candidate_refine)
             if self._exact_collision[0]:   # (after the collision model, the world and the cloud)
@@ -256,6 +259,42 @@ class IKFlowSolver:
         self._push_collision_model(eng)
         eng.set_world_cloud(*self._world_cloud)
 
+    def set_world_track(self, worlds, min_clearance: float = 0.0):
+        """A scene that moves along the path: one ikflow_amd.world.World per waypoint of generate_ik_path (None or an empty sequence: no track),
+        each holding the same obstacles - the same number, the same kinds in the same order; one that appears or disappears is moved far away.
+        While a track is set, generate_ik_path also drops candidate r of waypoint t when it is closer than min_clearance to frame t and - under
+        set_path_sweep - avoids every edge whose samples come closer than that to the frames interpolated between its two waypoints' frames
+        (include/ikflow_amd_track.h).  A path of more waypoints than frames is refused.  Beside set_world and set_world_cloud, which stay in force;
+        ranked and diverse IK do not read it.  Needs the robot's capsule model (Robot.set_collision_capsules)."""
+        from ikflow_amd.world import World
+
+        assert isinstance(min_clearance, (int, float)) and not isinstance(min_clearance, bool) and math.isfinite(min_clearance), (
+            f"min_clearance must be a finite number, got {min_clearance!r}")
+        if worlds is None or len(worlds) == 0:
+            self._world_track = None
+            if self._engine is not None:
+                self._engine.clear_world_track()
+            return
+        worlds = list(worlds)
+        assert all(isinstance(w, World) for w in worlds), "worlds must be a sequence of ikflow_amd.world.World"
+        assert len(worlds) <= 1024, f"a world track holds at most 1024 frames, got {len(worlds)}"
+        n = len(worlds[0])
+        assert n >= 1, "frame 0 holds no obstacle"
+        for t, w in enumerate(worlds):
+            assert len(w) == n, f"frame {t} holds {len(w)} obstacles, frame 0 holds {n}"
+            for o, (ob, ob0) in enumerate(zip(w.obstacles, worlds[0].obstacles)):
+                assert ob[0] == ob0[0], f"frame {t} obstacle {o}: kind {ob[0]} differs from frame 0's kind {ob0[0]}"
+        assert self._robot.has_collision_model, "set_world_track needs a collision model (Robot.set_collision_capsules)"
+        self._world_track = (worlds, float(min_clearance))
+        if self._engine is not None:
+            self._push_world_track(self._engine)
+        else:
+            self.engine()
+
+    def _push_world_track(self, eng):
+        self._push_collision_model(eng)
+        eng.set_world_track(*self._world_track)
+
     def set_path_sweep(self, n_samples: int):
         """Samples per edge of generate_ik_path's lattice (0: no sweep, the default; at most 16).  While set, the path also avoids every edge
         whose n_samples interpolated configurations - q_i = a + i / (n_samples + 1) * (b - a) - come closer to the world of set_world than its
@@ -318,6 +357,29 @@ class IKFlowSolver:
                 return torch.zeros(0, dtype=torch.bool, device=path.device)
             rows = path.to(torch.float32).contiguous()
             return eng.sweep_edges(rows[:-1].contiguous(), rows[1:].contiguous(), n_samples, reject_self, min_clearance)[0]
+
+    def timed_path_collides(self, path: torch.Tensor, q_start: Optional[torch.Tensor] = None, reject_self: bool = False,
+                            min_clearance: float = 0.0) -> torch.Tensor:
+        """The swept check of a TIMED joint-space path [T x ndof] - row t is where the robot is at waypoint t: the lattice of one candidate per
+        waypoint under the solver's sweep (set_path_sweep, at least 1), world, world track and - reject_self - the robot itself with
+        min_clearance.  -> [T] bool: entry t >= 1, whether the edge path[t - 1] -> path[t] is blocked; entry 0, whether q_start -> path[0] is
+        (False without q_start).  The rows themselves are not tested (Engine.world_track_clearance does that for the track)."""
+        assert isinstance(path, torch.Tensor) and path.ndim == 2 and path.shape[1] == self.ndof, f"path must be [T x {self.ndof}]"
+        assert q_start is None or (isinstance(q_start, torch.Tensor) and tuple(q_start.shape) == (self.ndof,)), f"q_start must be [{self.ndof}]"
+        assert self._path_sweep >= 1, "timed_path_collides needs a sweep (set_path_sweep)"
+        assert self._robot.has_collision_model, "timed_path_collides needs a collision model (Robot.set_collision_capsules)"
+        with torch.inference_mode():
+            eng = self.engine(path.device)
+            self._push_collision_model(eng)
+            T = path.shape[0]
+            if T == 0:
+                return torch.zeros(0, dtype=torch.bool, device=path.device)
+            rows = path.to(torch.float32).contiguous()
+            start = None if q_start is None else q_start.to(device=path.device, dtype=torch.float32).contiguous()
+            edge_free, start_free = eng.sweep_lattice(rows, T, 1, start, reject_self, min_clearance)
+            blocked = ~edge_free[:, 0, 0]
+            blocked[0] = False if start_free is None else ~start_free[0]
+            return blocked
 
     def set_precision(self, mode: str):
         """Arithmetic of the hidden Linear contractions: "f32" (exact f32 MFMA, default) or "f16x3" (error-compensated

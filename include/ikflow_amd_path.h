@@ -23,6 +23,7 @@
  * r with cost[t][r] < +inf (where a path breaks), node_cost_out the node costs in the candidate layout (unweighted).  No path (total +inf):
  * path rows 0, indices -1, cost +inf.
  * Refined candidates: while a refinement is set on the handle (include/ikflow_amd_refine.h), ikf_generate_path builds its lattice from LM-refined rows.
+ * A world that moves along the path - one frame of obstacles per waypoint - is include/ikflow_amd_track.h.
  */
 #ifndef IKFLOW_AMD_PATH_H
 #define IKFLOW_AMD_PATH_H

@@ -26,7 +26,7 @@
  *
  * Resolution: with max_joint_step = s >= 0, consecutive tested configurations of an admitted edge differ by at most s / (S + 1) per joint.
  * The sweep is SAMPLED, not conservative: what the arm crosses between two samples is not seen.  The caller covers that gap with
- * min_clearance.
+ * min_clearance.  Obstacles that move along the path are a world track (include/ikflow_amd_track.h), swept beside these rules.
  */
 #ifndef IKFLOW_AMD_SWEEP_H
 #define IKFLOW_AMD_SWEEP_H

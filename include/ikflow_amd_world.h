@@ -24,6 +24,7 @@
  * min_clearance - whatever reject_collisions says: that flag and the options' own min_clearance keep meaning the robot against itself.
  * Path IK tests its nodes; the configurations along its edges only while a sweep is set (include/ikflow_amd_sweep.h).
  * Exact IK obeys the world only while the exact collision rule is on (include/ikflow_amd_exact_world.h).
+ * These obstacles stand still; obstacles that move along a path are a world track (include/ikflow_amd_track.h).
  */
 #ifndef IKFLOW_AMD_WORLD_H
 #define IKFLOW_AMD_WORLD_H
