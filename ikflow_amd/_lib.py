@@ -301,6 +301,17 @@ TRACK_SIGNATURES = {
     "ikf_sweep_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
+# ... every symbol include/ikflow_amd_manip.h declares (singularity rule: a floor under the manipulability measure of a candidate)
+IKF_MANIP_FULL, IKF_MANIP_LINEAR, IKF_MANIP_ANGULAR = 0, 1, 2
+MANIP_PARTS = {"full": IKF_MANIP_FULL, "linear": IKF_MANIP_LINEAR, "angular": IKF_MANIP_ANGULAR}
+MANIP_SIGNATURES = {
+    # part, min_manipulability
+    "ikf_set_min_manipulability": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "ikf_min_manipulability": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    # q, n, part, min_manipulability, w_out, below_out, stream
+    "ikf_manipulability": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 LIB_PATH = _build.LIB_PATH
 _libs = {}
 
@@ -324,7 +335,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(MANIP_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -86,6 +86,19 @@ ikf_status ikf::score_candidates(ikf_model* m, const float* d_poses, int64_t n, 
     a.cloud_clearance = m->cloud_row.p;
     a.cloud_min_clearance = m->cloud_min_clearance;
   }
+  // With a manipulability floor set on the handle (ikf_set_min_manipulability) the same buffer is the rows' gate: k_manip_rows puts -inf on every
+  // row below the floor - under any cloud threshold, which is finite - and leaves the clearances of the others; with no cloud it writes -inf / +inf
+  // against a threshold of 0.
+  if (m->manip_min > 0.f) {
+    const long long rows = n * (long long)k;
+    IKF_HIP(m->cloud_row.ensure(rows));
+    IKF_HIP(launch_manip_rows(m->d_chain, m->dims.ndof, d_q, rows, m->manip_part, m->manip_min, nullptr, nullptr, m->cloud_row.p,
+                              m->cloud_n > 0 ? 1 : 0, s));
+    if (m->cloud_n == 0) {
+      a.cloud_clearance = m->cloud_row.p;
+      a.cloud_min_clearance = 0.f;
+    }
+  }
   a.row_score = d_row_score;
   a.q_out = d_q_out;
   a.score_out = d_score_out;
@@ -149,10 +162,8 @@ ikf_status ikf::reserve_candidates(ikf_model* m, const char* who, const char* ru
   const long long rows = max_poses * (long long)max_k;
   ikf_status st = ensure_rank_rows(m, rows);
   if (st == IKF_OK) st = ensure_rank_lists(m, max_poses);
-  if (st == IKF_OK && m->cloud_n > 0) {   // the rows' cloud clearances and their partial minima, under the cloud that is set now
-    IKF_HIP(m->cloud_row.ensure(rows));
-    st = ensure_cloud_partials(m, rows);
-  }
+  if (st == IKF_OK && (m->cloud_n > 0 || m->manip_min > 0.f)) IKF_HIP(m->cloud_row.ensure(rows));   // the rows' gate, under the cloud / the floor set now
+  if (st == IKF_OK && m->cloud_n > 0) st = ensure_cloud_partials(m, rows);   // the cloud's partial minima
   if (st == IKF_OK && m->loaded) st = ikf_reserve(m, rows);   // the flow's scratch (and, where that path can be reached, its weight image)
   return st;
 }

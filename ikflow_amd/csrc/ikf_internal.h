@@ -16,6 +16,7 @@
 #include "track_math.h"
 #include "refine_math.h"
 #include "exact_world_math.h"
+#include "manip_math.h"
 #include "flow_plan.h"  // IKF_RO_ROWS, the planner and the cluster back-off (host arithmetic, no HIP)
 
 namespace ikf {
@@ -489,8 +490,10 @@ struct RankArgs {
   int cap_stride;             // floats of capsule scratch per thread (odd: bank spread), 0 without collisions and without a world
   const WorldModel* world;    // the handle's obstacles (world_math.h), or null: no world rule
   float world_min_clearance;  // read only with a world
-  const float* cloud_clearance;  // [k * m] the rows' cloud clearances (cloud_kernels.hip), or null: no cloud rule
-  float cloud_min_clearance;  // read only with cloud clearances
+  const float* cloud_clearance;  // [k * m] the rows' GATE, or null: no such rule - a row whose value is < cloud_min_clearance scores +inf.  With a cloud
+                              // the rows' cloud clearances (cloud_kernels.hip), -inf on the rows under the manipulability floor; with a floor
+                              // alone -inf / +inf (manip_kernels.hip)
+  float cloud_min_clearance;  // read only with a gate: the cloud's threshold (finite), 0 with a floor alone
   float* row_score;           // [k * m], or null
   // one chunk: stage 1 writes the final outputs; more: the partial lists below, merged by k_rank_merge
   float* q_out;               // [m][n_keep][ndof]
@@ -631,5 +634,10 @@ struct ExactClearArgs {
 hipError_t launch_exact_lm_iters_clear(const ExactClearArgs& a, int ndof, hipStream_t s);
 hipError_t launch_exact_mask_rows(uint8_t* row_valid_iter, const float* cloud_clearance, float cloud_min, long long rows,
                                   unsigned long long* rejected_rows, hipStream_t s);
+
+// manip_kernels.hip - singularity rule (include/ikflow_amd_manip.h; the arithmetic: manip_math.h).  The three sinks are nullable: w_out and
+// below_out [n]; gate [n] - -inf on a row below `floor`, on a passing row what it holds (gate_keep) or +inf.
+hipError_t launch_manip_rows(const Chain* d_chain, int ndof, const float* q, long long n, int part, float floor, float* w_out, uint8_t* below_out,
+                             float* gate, int gate_keep, hipStream_t s);
 
 }  // namespace ikf

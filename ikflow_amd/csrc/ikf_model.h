@@ -1,6 +1,6 @@
 // The handle behind the C-ABI (struct ikf_model) and what the API units api_handle / api_weights / api_flow / api_kin share: error
 // reporting, the device and stream scopes, the profiling mark, and the few host functions that cross a unit boundary.  Included by
-// those units (and api_rank / api_path / api_diverse / api_world / api_cloud / api_sweep / api_refine / api_exact_world) only; the kernel-launch interface is ikf_internal.h.
+// those units (and api_rank / api_path / api_diverse / api_world / api_cloud / api_sweep / api_refine / api_exact_world / api_manip) only; the kernel-launch interface is ikf_internal.h.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -208,8 +208,12 @@ struct ikf_model {
   DeviceBuf<CloudPoint> d_cloud;  // [cloud_n rounded up to IKF_CLOUD_TILE] (x, y, z, 0), the padding copies of the last point
   long long cloud_n = 0;
   float cloud_radius = 0.f, cloud_min_clearance = 0.f;
-  DeviceBuf<float> cloud_row;     // [rows] the candidate rows' cloud clearances (score_candidates)
+  DeviceBuf<float> cloud_row;     // [rows] the candidate rows' GATE (score_candidates): their cloud clearances while a cloud is set, with -inf on the
+                                  // rows under the manipulability floor; -inf / +inf with a floor and no cloud
   DeviceBuf<float> cloud_part;    // [chunks][rows] partial minima of a call whose plan has more than one chunk
+  // singularity rule (api_manip.hip, api_rank.hip): with manip_min > 0 the candidate stage also rejects rows whose measure of manip_part is not >= it
+  int manip_part = IKF_MANIP_FULL;
+  float manip_min = 0.f;
   // f16x3 range guard
   DeviceBuf<int> d_split_flag;    // device word OR'ed by every kernel that produces a split operand out of the f16 range
   PinnedBuf<int> h_split_flag;    // pinned host

@@ -422,6 +422,33 @@ class Engine:
             self._ck(self.lib.ikf_cloud_clearance(self._h, q.data_ptr(), n, dist.data_ptr(), col.data_ptr(), self._stream()))
         return dist, col.to(torch.bool)
 
+    # -- singularity rule (include/ikflow_amd_manip.h) ---------------------------------------------------------
+    def set_min_manipulability(self, min_manipulability: float, part: str = "full") -> None:
+        """A floor under the manipulability measure of `part` ("full", "linear", "angular") of every candidate (0: no rule, the default).  While
+        a floor is set, rank_candidates / generate_ranked, path_search / generate_path and diverse_select / generate_diverse also drop every
+        candidate whose measure is not >= it - under set_candidate_refine the refined one's.  Not while calls on this engine are in flight on
+        another stream."""
+        self._ck(self.lib.ikf_set_min_manipulability(self._h, _lib.MANIP_PARTS[part], float(min_manipulability)))
+
+    @property
+    def min_manipulability(self) -> Tuple[float, str]:
+        """-> (floor, part) in force on this engine; floor 0: no rule."""
+        part, floor = C.c_int(0), C.c_float(0.0)
+        self._ck(self.lib.ikf_min_manipulability(self._h, C.byref(part), C.byref(floor)))
+        return float(floor.value), {v: k for k, v in _lib.MANIP_PARTS.items()}[part.value]
+
+    def manipulability(self, q: torch.Tensor, part: str = "full", min_manipulability: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """[n x ndof] -> (w [n] f32: sqrt(det(J J^T)) over the rows of `part` of the geometric Jacobian - J^T J for a chain of fewer joints than
+        rows -, not (w >= min_manipulability) [n] bool).  The call's own floor: the engine's set_min_manipulability state plays no part."""
+        q = self._q(q)
+        n = q.shape[0]
+        w = torch.empty(n, dtype=torch.float32, device=self.device)
+        below = torch.empty(n, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_manipulability(self._h, q.data_ptr(), n, _lib.MANIP_PARTS[part], float(min_manipulability), w.data_ptr(),
+                                                 below.data_ptr(), self._stream()))
+        return w, below.to(torch.bool)
+
     # -- swept collision checks along edges (include/ikflow_amd_sweep.h) ------------------------------------
     def set_path_sweep(self, n_samples: int) -> None:
         """Samples per lattice edge of path_search / generate_path (0: no sweep, the default; at most 16).  While a sweep is set, an edge

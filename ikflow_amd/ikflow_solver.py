@@ -135,6 +135,7 @@ class IKFlowSolver:
         self._world_track = None  # (worlds, min_clearance) of set_world_track: likewise (pushed after the collision model, the world and the sweep)
         self._candidate_refine = (0, 0.0, 0.0)  # (n_steps, pos_tol, rot_tol) of set_candidate_refine: likewise
         self._exact_collision = (False, False, 0.0)  # (enabled, reject_self_collisions, min_clearance) of set_exact_collision: likewise
+        self._min_manipulability = (0.0, "full")  # (floor, part) of set_min_manipulability: likewise
         # tests / tools only: "probes" binds lib/libikflow_amd_probes.so (the product + the priced-and-rejected forms of rounds 2 - 3);
         # set before the first call
         self.library_flavour = ""
@@ -191,6 +192,8 @@ class IKFlowSolver:
                 self._push_world_track(eng)
             if self._candidate_refine[0]:
                 eng.set_candidate_refine(*self._candidate_refine)
+            if self._min_manipulability[0]:
+                eng.set_min_manipulability(*self._min_manipulability)
             if self._exact_collision[0]:   # (after the collision model, the world and the cloud)
                 self._push_exact_collision(eng)
             self._engine = eng
@@ -318,6 +321,20 @@ class IKFlowSolver:
         self._candidate_refine = (n_steps, float(pos_tol), float(rot_tol)) if n_steps else (0, 0.0, 0.0)
         if self._engine is not None:
             self._engine.set_candidate_refine(*self._candidate_refine)
+
+    def set_min_manipulability(self, min_manipulability: float, part: str = "full"):
+        """A floor under Yoshikawa's manipulability measure w = sqrt(det(J J^T)) of every candidate of generate_ranked_ik_solutions,
+        generate_diverse_ik_solutions and generate_ik_path (0: no rule, the default): a candidate whose w is not >= the floor is inadmissible
+        like one beyond a limit - a near-singular configuration reaches the pose but cannot be left without large joint velocities.  part:
+        "full" (all six rows of the geometric Jacobian; mixes radians and metres), "linear" (rows 3-5) or "angular" (rows 0-2).  Under
+        set_candidate_refine the refined candidate is tested.  generate_exact_ik_solutions and the swept edges of set_path_sweep do not obey
+        the floor (include/ikflow_amd_manip.h)."""
+        assert isinstance(min_manipulability, (int, float)) and not isinstance(min_manipulability, bool) and math.isfinite(min_manipulability) \
+            and min_manipulability >= 0, f"min_manipulability must be a finite number >= 0, got {min_manipulability!r}"
+        assert part in ("full", "linear", "angular"), f'part must be "full", "linear" or "angular", got {part!r}'
+        self._min_manipulability = (float(min_manipulability), part)
+        if self._engine is not None:
+            self._engine.set_min_manipulability(*self._min_manipulability)
 
     def set_exact_collision(self, reject_self_collisions: bool = False, min_clearance: float = 0.0, enabled: bool = True):
         """Make generate_exact_ik_solutions obey the scene (off by default).  While enabled, a repeat whose solution - its configuration at the

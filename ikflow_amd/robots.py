@@ -258,6 +258,11 @@ class Robot:
         """[n x ndof] -> [n x 6 x ndof] geometric Jacobian, rows = [angular(3); linear(3)]."""
         return self._engine(q).jacobian(q)
 
+    def manipulability(self, q, part="full"):
+        """[n x ndof] -> [n] Yoshikawa's manipulability measure sqrt(det(J J^T)) over the rows of `part` of the geometric Jacobian: "full" (all
+        six), "linear" (rows 3-5) or "angular" (rows 0-2); J^T J for a chain of fewer joints than rows.  fp64 inside, f32 out."""
+        return self._engine(q).manipulability(q, part)[0]
+
     # -- capsule self-collision model (jrl.Robot.config_self_collides / self_collision_distances mechanism) ---------
     def set_collision_capsules(self, capsules, ignored_pairs=()):
         """Attach a capsule collision model.  No geometry ships with the built-in robots: jrl's capsule tables are not
