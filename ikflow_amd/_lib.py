@@ -228,6 +228,21 @@ PATH_SIGNATURES = {
     "ikf_reserve_path": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
 }
 
+# ... every symbol include/ikflow_amd_path_batch.h declares (path IK for P paths per call: the candidate layout over P * T waypoints)
+PATH_BATCH_SIGNATURES = {
+    # m, waypoints, P, T, k, q, q_start, opt, outputs, stream
+    "ikf_path_search_batch": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ikf_path_options)] + _PATH_OUTPUTS + [C.c_void_p],
+    ),
+    # m, waypoints, P, T, k, latent, shared_latent, clamp_to_limits, q_start, opt, outputs, stream
+    "ikf_generate_path_batch": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(ikf_path_options)] + _PATH_OUTPUTS + [C.c_void_p],
+    ),
+    "ikf_reserve_path_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+}
+
 # ... every symbol include/ikflow_amd_diverse.h declares (diverse-of-K IK: a far-apart set of each pose's admissible candidates)
 # q_out, score_out, index_out, separation_out, kept_out, count_out, row_score_out
 _DIVERSE_OUTPUTS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -335,7 +350,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(MANIP_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(PATH_BATCH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(MANIP_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

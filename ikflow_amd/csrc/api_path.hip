@@ -1,6 +1,7 @@
 // C-ABI of libikflow_amd.so, path IK (include/ikflow_amd_path.h): k candidates per waypoint - the caller's, or the flow's through the tiling
 // pose source of the exact path - scored by the ranking kernel and searched by k_path_lattice (path_kernels.hip).  The frame of api_rank.hip: stream
-// scope, handle-owned buffers grown on demand (the candidate rows are the ranking's), nothing read back to the host.
+// scope, handle-owned buffers grown on demand (the candidate rows are the ranking's), nothing read back to the host.  The last section is the same
+// for P paths per call (include/ikflow_amd_path_batch.h): the candidate stage on P * T waypoints, the BATCH forms of the sweep and the lattice.
 #include "ikf_model.h"
 
 // node costs [rows] and back-pointers (a byte per node) of a lattice of up to `rows` nodes
@@ -33,17 +34,21 @@ static ikf_status path_check(ikf_model* m, const char* who, int64_t T, int k, co
                           d_waypoints && d_rows && d_path_out && d_index_out && d_cost_out, nothing_to_do);
 }
 
-static ikf_status run_path(ikf_model* m, const float* d_waypoints, int64_t T, int k, const float* d_q, const float* d_q_start,
+// P == 0: one path of T waypoints.  P > 0 (include/ikflow_amd_path_batch.h): P paths of T waypoints in one candidate layout of n = P * T waypoints -
+// the candidate stage sees n poses, the sweep and the lattice are told where one path ends and the next begins (no world track: refused by the entries).
+static ikf_status run_path(ikf_model* m, const float* d_waypoints, int64_t P, int64_t T, int k, const float* d_q, const float* d_q_start,
                            const ikf_path_options* opt, float* d_path_out, int32_t* d_index_out, float* d_cost_out, int32_t* d_reachable_out,
                            float* d_node_cost_out, hipStream_t s) {
   // Node costs: the ranking kernel itself, the waypoints as its poses, n_keep = 1 - so node[t][r] IS ikf_rank_candidates' row score of the row.
   // Its one kept row per waypoint goes to d_path_out, which the lattice launch behind it overwrites in full.
+  const int64_t n = P > 0 ? P * T : T;
   float* const node = d_node_cost_out ? d_node_cost_out : m->pt_node.p;
-  ikf_status st = score_candidates(m, d_waypoints, T, k, d_q, nullptr, scoring_options(*opt), d_path_out, nullptr, nullptr, nullptr, node, s);
+  ikf_status st = score_candidates(m, d_waypoints, n, k, d_q, nullptr, scoring_options(*opt), d_path_out, nullptr, nullptr, nullptr, node, s);
   if (st != IKF_OK) return st;
-  st = track_mask_nodes(m, d_q, T, k, node, s);   // a world track: +inf in place where a row hits its waypoint's key frame; nothing without one
+  st = track_mask_nodes(m, d_q, n, k, node, s);   // a world track: +inf in place where a row hits its waypoint's key frame; nothing without one
   if (st != IKF_OK) return st;
   PathArgs a{};
+  a.P = (int)P;
   a.q = d_q;
   a.q_start = d_q_start;
   a.opt = *opt;
@@ -71,6 +76,7 @@ static ikf_status run_path(ikf_model* m, const float* d_waypoints, int64_t T, in
     w.q_start = d_q_start;
     w.node = node;
     w.T = (int)T;
+    w.P = (int)P;
     w.k = k;
     w.max_joint_step = opt->max_joint_step;
     w.edge_free = m->pt_edge_free.p;
@@ -102,7 +108,7 @@ extern "C" ikf_status ikf_path_search(ikf_model* m, const float* d_waypoints, in
   hipStream_t s = static_cast<hipStream_t>(stream);
   StreamScope scope(m, s);
   IKF_HIP(scope.enter());
-  st = run_path(m, d_waypoints, T, k, d_q, d_q_start, opt, d_path_out, d_index_out, d_cost_out, d_reachable_out, d_node_cost_out, s);
+  st = run_path(m, d_waypoints, 0, T, k, d_q, d_q_start, opt, d_path_out, d_index_out, d_cost_out, d_reachable_out, d_node_cost_out, s);
   if (st != IKF_OK) return st;
   IKF_HIP(scope.leave());
   return IKF_OK;
@@ -134,7 +140,7 @@ extern "C" ikf_status ikf_generate_path(ikf_model* m, const float* d_waypoints, 
   }
   st = flow_candidates(m, d_waypoints, T, k, d_latent, clamp_to_limits, s);
   if (st != IKF_OK) return st;
-  st = run_path(m, d_waypoints, T, k, m->rk_q.p, d_q_start, opt, d_path_out, d_index_out, d_cost_out, d_reachable_out, d_node_cost_out, s);
+  st = run_path(m, d_waypoints, 0, T, k, m->rk_q.p, d_q_start, opt, d_path_out, d_index_out, d_cost_out, d_reachable_out, d_node_cost_out, s);
   if (st != IKF_OK) return st;
   IKF_HIP(scope.leave());
   return IKF_OK;
@@ -152,5 +158,100 @@ extern "C" ikf_status ikf_reserve_path(ikf_model* m, int64_t max_waypoints, int 
   if (st == IKF_OK && m->track_F > 0) {   // a world track set by now: the zero node costs of ikf_sweep_lattice (its fine table was sized when it was set)
     IKF_HIP(m->tk_zero_node.ensure(rows));
   }
+  return st;
+}
+
+// ---- P paths per call (include/ikflow_amd_path_batch.h): the candidate stage with n = P * T poses, one lattice workgroup per path --------------------
+
+// node costs [k * P * T] and P blocks of back-pointers (path_batch_math.h); both monotone in P, T and k, so a reservation covers every smaller call
+static ikf_status ensure_path_batch_scratch(ikf_model* m, long long P, long long T, int k) {
+  IKF_HIP(m->pt_node.ensure(P * T * k));
+  IKF_HIP(m->pt_bp.ensure(path_batch_bp_bytes(P, T, k)));
+  return IKF_OK;
+}
+// P * T as the candidate stage's pose count: -1 when either is negative, 0 when either is 0, 2^31 (refused as too large) beyond the range
+static int64_t path_batch_count(int64_t P, int64_t T) {
+  if (P < 0 || T < 0) return -1;
+  if (P == 0 || T == 0) return 0;
+  if (P > 0x7fffffffLL || T > 0x7fffffffLL || P * T > 0x7fffffffLL) return 0x80000000LL;
+  return P * T;
+}
+// the checks of a single path call on P * T waypoints, then the one rule of the batch: no world track
+static ikf_status path_batch_check(ikf_model* m, const char* who, int64_t P, int64_t T, int k, const ikf_path_options* opt, const void* d_waypoints,
+                                   const void* d_rows, const void* d_path_out, const void* d_index_out, const void* d_cost_out, bool* nothing_to_do) {
+  const bool bad_weight = opt && !(opt->node_weight >= 0.f);
+  ikf_status st = check_candidates(m, who, "P * T", path_batch_count(P, T), k, IKF_PATH_MAX_K, opt, opt && opt->reject_collisions,
+                                   bad_weight ? "node_weight must be >= 0" : nullptr,
+                                   d_waypoints && d_rows && d_path_out && d_index_out && d_cost_out, nothing_to_do);
+  if (st != IKF_OK || *nothing_to_do) return st;
+  if (m->track_F > 0)
+    return fail(IKF_ERR_BAD_ARGUMENT, std::string(who) + ": a world track is set (ikf_set_world_track); frames per batched path are not covered - "
+                                                         "clear the track or call the single-path entry per path");
+  return IKF_OK;
+}
+
+extern "C" ikf_status ikf_path_search_batch(ikf_model* m, const float* d_waypoints, int64_t P, int64_t T, int k, const float* d_q,
+                                            const float* d_q_start, const ikf_path_options* opt, float* d_path_out, int32_t* d_index_out,
+                                            float* d_cost_out, int32_t* d_reachable_out, float* d_node_cost_out, void* stream) {
+  if (!m) return fail(IKF_ERR_NULL_POINTER, "ikf_path_search_batch: null model");
+  bool nothing = false;
+  ikf_status st = path_batch_check(m, "ikf_path_search_batch", P, T, k, opt, d_waypoints, d_q, d_path_out, d_index_out, d_cost_out, &nothing);
+  if (st != IKF_OK || nothing) return st;
+  IKF_ON_DEVICE(m)
+  const long long rows = P * T * (long long)k;
+  st = ensure_path_batch_scratch(m, P, T, k);
+  if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, rows, k);
+  if (st != IKF_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  StreamScope scope(m, s);
+  IKF_HIP(scope.enter());
+  st = run_path(m, d_waypoints, P, T, k, d_q, d_q_start, opt, d_path_out, d_index_out, d_cost_out, d_reachable_out, d_node_cost_out, s);
+  if (st != IKF_OK) return st;
+  IKF_HIP(scope.leave());
+  return IKF_OK;
+}
+
+extern "C" ikf_status ikf_generate_path_batch(ikf_model* m, const float* d_waypoints, int64_t P, int64_t T, int k, const float* d_latent,
+                                              int shared_latent, int clamp_to_limits, const float* d_q_start, const ikf_path_options* opt,
+                                              float* d_path_out, int32_t* d_index_out, float* d_cost_out, int32_t* d_reachable_out,
+                                              float* d_node_cost_out, void* stream) {
+  ikf_status st = check_ready(m, "ikf_generate_path_batch");
+  if (st != IKF_OK) return st;
+  bool nothing = false;
+  st = path_batch_check(m, "ikf_generate_path_batch", P, T, k, opt, d_waypoints, d_latent, d_path_out, d_index_out, d_cost_out, &nothing);
+  if (st != IKF_OK || nothing) return st;
+  IKF_ON_DEVICE(m)
+  const long long n = P * T, rows = n * k;
+  st = ensure_rank_rows(m, rows);
+  if (st == IKF_OK) st = ensure_path_batch_scratch(m, P, T, k);
+  if (st == IKF_OK && shared_latent) st = ensure_path_latent(m, rows);
+  if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, rows, k);
+  if (st != IKF_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  StreamScope scope(m, s);
+  IKF_HIP(scope.enter());
+  if (shared_latent) {   // candidate r uses latent r at every waypoint of every path: the single path's expansion over P * T waypoints
+    IKF_HIP(launch_path_expand_latent(d_latent, k, n, m->dims.D, m->pt_latent.p, s));
+    d_latent = m->pt_latent.p;
+  }
+  st = flow_candidates(m, d_waypoints, n, k, d_latent, clamp_to_limits, s);
+  if (st != IKF_OK) return st;
+  st = run_path(m, d_waypoints, P, T, k, m->rk_q.p, d_q_start, opt, d_path_out, d_index_out, d_cost_out, d_reachable_out, d_node_cost_out, s);
+  if (st != IKF_OK) return st;
+  IKF_HIP(scope.leave());
+  return IKF_OK;
+}
+
+extern "C" ikf_status ikf_reserve_path_batch(ikf_model* m, int64_t max_paths, int64_t max_waypoints, int max_k) {
+  if (!m) return fail(IKF_ERR_NULL_POINTER, "ikf_reserve_path_batch: null model");
+  const char* const rule = "max_paths and max_waypoints must be positive and max_k in 1 .. 256 (product < 2^31)";
+  if (max_paths < 1 || max_waypoints < 1) return fail(IKF_ERR_BAD_ARGUMENT, std::string("ikf_reserve_path_batch: ") + rule);
+  ikf_status st = reserve_candidates(m, "ikf_reserve_path_batch", rule, path_batch_count(max_paths, max_waypoints), max_k, IKF_PATH_MAX_K);
+  if (st != IKF_OK) return st;
+  IKF_ON_DEVICE(m)
+  const long long rows = max_paths * max_waypoints * (long long)max_k;
+  st = ensure_path_batch_scratch(m, max_paths, max_waypoints, max_k);
+  if (st == IKF_OK && m->loaded) st = ensure_path_latent(m, rows);
+  if (st == IKF_OK && m->path_sweep > 0) st = ensure_path_mask(m, rows, max_k);   // (a sweep set later sizes its mask at the first call)
   return st;
 }

@@ -13,6 +13,7 @@
 #include "world_math.h"
 #include "cloud_math.h"
 #include "sweep_math.h"
+#include "path_batch_math.h"  // batched path IK: where a path begins in the candidate layout, the back-pointers and the mask (no HIP)
 #include "track_math.h"
 #include "refine_math.h"
 #include "exact_world_math.h"
@@ -520,6 +521,10 @@ struct PathArgs {
   float* cost_out;            // [1]
   int* reachable_out;         // [T], or null
   const uint64_t* edge_free;  // [T][k][sweep_words(k)] the sweep's verdicts (sweep_math.h), or null: no sweep - the lattice kernel as it was
+  // Batched (include/ikflow_amd_path_batch.h; path_batch_math.h): P > 0 - P paths of T waypoints in one layout of P * T waypoints, a workgroup per
+  // path.  q, node and edge_free are then laid out over P * T waypoints, q_start is [P][ndof], bp holds P blocks of path_batch_bp_stride(T, k)
+  // bytes, path_out / index_out / reachable_out are [P * T] and cost_out is [P].  P == 0: the single path above, the kernel as it was.
+  int P;
 };
 hipError_t launch_path_expand_latent(const float* latent, int k, long long T, int D, float* out, hipStream_t s);
 hipError_t launch_path_lattice(int ndof, const PathArgs& a, hipStream_t s);
@@ -582,6 +587,9 @@ struct SweepArgs {
   const WorldObstacle* track; // [track_fine_frames(track_frames, n_samples)][n_track] the fine table, built for n_samples
   int n_track, track_frames;  // obstacles per frame, key frames (T <= track_frames)
   float track_min_clearance;
+  // lattice source over a batch (path_batch_math.h): P > 0 - q, node and edge_free over P * T waypoints, q_start [P][ndof]; never with a track.
+  // P == 0: one lattice, the kernel as it was.
+  int P;
 };
 hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s);
 

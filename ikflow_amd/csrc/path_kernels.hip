@@ -20,6 +20,11 @@
 //   registers; those of the next stage are loaded with the stage prefetch that is in flight anyway, not on the sequential chain (at most
 //   4 x 64 bit per thread and waypoint).  Bit j is tested before predecessor j is offered to path_relax, bit 0 of row 0 before path_start with
 //   a q_start.  SWEEP = false is the kernel as it was.
+// BATCH (include/ikflow_amd_path_batch.h): P paths of T waypoints in one candidate layout of P * T waypoints, grid = P, ONE workgroup per path with
+//   the geometry and the LDS plan above.  Workgroup p shifts its arguments to its own path (path_batch_view: waypoints p T .. p T + T - 1, its
+//   q_start, its block of back-pointers, its outputs, its mask words) and runs the single path's code with the batch's row stride P T - the
+//   waypoints of a path stay adjacent, so a stage is still k contiguous segments.  No workgroup reads what another writes; no atomics.
+//   BATCH = false is the kernel as it was.
 #include "ikf_internal.h"
 
 namespace ikf {
@@ -39,18 +44,20 @@ constexpr size_t kPathLatticeLds = sizeof(float) * (4 * (size_t)kPathRowVecs + 2
 static_assert(kPathLatticeLds <= 64 * 1024, "the lattice workgroup's static LDS");
 static_assert((size_t)IKF_PATH_BT_CHUNK * IKF_PATH_MAX_K + 4 <= sizeof(float) * 4 * (size_t)kPathRowVecs, "a chunk of back-pointers must fit the row buffers");
 
-// the rows and node costs of waypoints t0 .. t0 + wn - 1 into registers: element i = thread + 256 u of the k segments of wn * NDOF floats
+// the rows and node costs of waypoints t0 .. t0 + wn - 1 into registers: element i = thread + 256 u of the k segments of wn * NDOF floats;
+// `stride`: waypoints between two candidates of one waypoint (T; P * T in a batch, where consecutive waypoints of a path are still adjacent)
 template <int NDOF>
-__device__ __forceinline__ void path_stage_load(const PathArgs& a, long long t0, int wn, float (&pre)[IKF_PATH_STAGE * NDOF], float (&prn)[IKF_PATH_STAGE]) {
+__device__ __forceinline__ void path_stage_load(const PathArgs& a, long long stride, long long t0, int wn, float (&pre)[IKF_PATH_STAGE * NDOF],
+                                                float (&prn)[IKF_PATH_STAGE]) {
   const int seg = wn * NDOF;
 #pragma unroll
   for (int u = 0; u < IKF_PATH_STAGE * NDOF; ++u) {
     const int i = (int)threadIdx.x + IKF_PATH_BLOCK * u;
     const int r = i / seg, e = i - r * seg;
-    pre[u] = r < a.k ? a.q[((long long)r * a.T + t0) * NDOF + e] : 0.f;
+    pre[u] = r < a.k ? a.q[((long long)r * stride + t0) * NDOF + e] : 0.f;
   }
 #pragma unroll
-  for (int w = 0; w < IKF_PATH_STAGE; ++w) prn[w] = ((int)threadIdx.x < a.k && w < wn) ? a.node[(long long)threadIdx.x * a.T + t0 + w] : rank_inf();
+  for (int w = 0; w < IKF_PATH_STAGE; ++w) prn[w] = ((int)threadIdx.x < a.k && w < wn) ? a.node[(long long)threadIdx.x * stride + t0 + w] : rank_inf();
 }
 template <int NDOF>
 __device__ __forceinline__ void path_stage_store(const PathArgs& a, int buf, int wn, const float (&pre)[IKF_PATH_STAGE * NDOF], const float (&prn)[IKF_PATH_STAGE],
@@ -87,8 +94,30 @@ __device__ __forceinline__ bool path_mask_bit(const unsigned long long (&m)[IKF_
   return (word >> (j % IKF_SWEEP_LANES)) & 1ULL;
 }
 
+// What workgroup `p` of a batched launch works on: the arguments of its own path inside the layout of P * T waypoints (path_batch_math.h).  From
+// here on the path is addressed as a single one with the batch's row stride.
 template <int NDOF, bool SWEEP>
-__global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs a) {
+__device__ __forceinline__ PathArgs path_batch_view(const PathArgs& b, long long p) {
+  PathArgs a = b;
+  const long long g0 = path_batch_offset(p, b.T);
+  a.q += g0 * NDOF;
+  a.node += g0;
+  if (a.q_start) a.q_start += p * NDOF;
+  a.bp += path_batch_bp_offset(p, b.T, b.k);
+  a.path_out += g0 * NDOF;
+  a.index_out += g0;
+  a.cost_out += p;
+  if (a.reachable_out) a.reachable_out += g0;
+  if constexpr (SWEEP) a.edge_free += path_batch_mask_offset(p, b.T, b.k);
+  return a;
+}
+
+template <int NDOF, bool SWEEP, bool BATCH>
+__global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs a0) {
+  PathArgs view{};
+  if constexpr (BATCH) view = path_batch_view<NDOF, SWEEP>(a0, blockIdx.x);
+  const PathArgs& a = BATCH ? view : a0;
+  const long long stride = BATCH ? path_batch_waypoints(a0.P, a0.T) : (long long)a0.T;   // waypoints between two candidates of a waypoint
   __shared__ float4 s_rows[kPathRowVecs];                               // [2][STAGE][256] rows of 8 floats
   __shared__ float s_node[2 * IKF_PATH_STAGE * IKF_PATH_BLOCK];        // [2][STAGE][256]
   __shared__ float s_cost[2 * IKF_PATH_BLOCK];                          // [parity of t][256]
@@ -121,7 +150,7 @@ __global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs 
   {
     const int wn0 = T < IKF_PATH_STAGE ? (int)T : IKF_PATH_STAGE;
     if constexpr (SWEEP) path_mask_load(a, 0, wn0, r, live, mwords, mask_next);
-    path_stage_load<NDOF>(a, 0, wn0, pre, prn);
+    path_stage_load<NDOF>(a, stride, 0, wn0, pre, prn);
     path_stage_store<NDOF>(a, 0, wn0, pre, prn, rows, s_node);
   }
   __syncthreads();
@@ -139,7 +168,7 @@ __global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs 
         for (int x = 0; x < kPathMaskWords; ++x) mask[w][x] = mask_next[w][x];
       if (more) path_mask_load(a, t0 + IKF_PATH_STAGE, wn_next, r, live, mwords, mask_next);
     }
-    if (more) path_stage_load<NDOF>(a, t0 + IKF_PATH_STAGE, wn_next, pre, prn);   // in flight while this stage is relaxed
+    if (more) path_stage_load<NDOF>(a, stride, t0 + IKF_PATH_STAGE, wn_next, pre, prn);   // in flight while this stage is relaxed
     for (int w = 0; w < wn; ++w) {
       const long long t = t0 + w;
       const int cb = (int)(t & 1), pb = cb ^ 1;
@@ -222,7 +251,7 @@ __global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs 
     const long long tc = c * IKF_PATH_BT_CHUNK;
     const int n = T - tc < IKF_PATH_BT_CHUNK ? (int)(T - tc) : IKF_PATH_BT_CHUNK;
     __syncthreads();   // every reader of s_carry, s_idx and the staged chunk is done
-    const uint32_t* const g = reinterpret_cast<const uint32_t*>(a.bp + tc * k);   // tc * k is a multiple of 64
+    const uint32_t* const g = reinterpret_cast<const uint32_t*>(a.bp + tc * k);   // tc * k is a multiple of 64 (BATCH: from the path's own aligned block)
     const int words = (n * k + 3) / 4;                                            // (the scratch is padded: path_bp_bytes)
     for (int i = tid; i < words; i += IKF_PATH_BLOCK) bpw[i] = g[i];
     __syncthreads();
@@ -231,7 +260,7 @@ __global__ __launch_bounds__(IKF_PATH_BLOCK) void k_path_lattice(const PathArgs 
     for (int i = tid; i < n; i += IKF_PATH_BLOCK) a.index_out[tc + i] = s_idx[i];
     for (int i = tid; i < n * NDOF; i += IKF_PATH_BLOCK) {
       const int w = i / NDOF, d = i - w * NDOF;
-      a.path_out[(tc + w) * NDOF + d] = a.q[((long long)s_idx[w] * T + tc + w) * NDOF + d];
+      a.path_out[(tc + w) * NDOF + d] = a.q[((long long)s_idx[w] * stride + tc + w) * NDOF + d];
     }
   }
 }
@@ -244,16 +273,26 @@ hipError_t launch_path_expand_latent(const float* latent, int k, long long T, in
 }
 
 static bool path_args_ok(const PathArgs& a) {
-  return a.T >= 1 && a.k >= 1 && a.k <= IKF_PATH_MAX_K && (long long)a.k * a.T <= 0x7fffffffLL && a.q && a.node;
+  const long long paths = a.P > 0 ? a.P : 1;
+  return a.T >= 1 && a.k >= 1 && a.k <= IKF_PATH_MAX_K && a.P >= 0 && (long long)a.k * a.T * paths <= 0x7fffffffLL && a.q && a.node;
 }
 
 hipError_t launch_path_lattice(int ndof, const PathArgs& a, hipStream_t s) {
   if (!path_args_ok(a) || !a.bp || !a.path_out || !a.index_out || !a.cost_out) return hipErrorInvalidValue;
-  if (a.edge_free) {
-    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND, true>), dim3(1), dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
+  if (a.P > 0) {   // batched: a workgroup per path (the grid's x extent holds any P that passed path_args_ok)
+    const dim3 grid((unsigned)a.P);
+    if (a.edge_free) {
+      IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND, true, true>), grid, dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
+      return hipErrorInvalidValue;
+    }
+    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND, false, true>), grid, dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
     return hipErrorInvalidValue;
   }
-  IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND, false>), dim3(1), dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
+  if (a.edge_free) {
+    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND, true, false>), dim3(1), dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
+    return hipErrorInvalidValue;
+  }
+  IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_path_lattice<ND, false, false>), dim3(1), dim3(IKF_PATH_BLOCK), 0, s, a); return hipGetLastError());
   return hipErrorInvalidValue;
 }
 

@@ -113,6 +113,6 @@ inline int path_slices(int k) { return IKF_PATH_BLOCK / path_span(k); }
 IKF_PATH_HOST_DEVICE long long path_stages(long long T) { return (T + IKF_PATH_STAGE - 1) / IKF_PATH_STAGE; }
 IKF_PATH_HOST_DEVICE long long path_bt_chunks(long long T) { return (T + IKF_PATH_BT_CHUNK - 1) / IKF_PATH_BT_CHUNK; }
 // bytes of the back-pointer scratch of a T x k lattice: a byte per node, rounded up so that the walk back may read whole words
-inline long long path_bp_bytes(long long T, int k) { return ((T * k + 3) / 4 + 1) * 4; }
+IKF_PATH_HOST_DEVICE long long path_bp_bytes(long long T, int k) { return ((T * k + 3) / 4 + 1) * 4; }
 
 }  // namespace ikf

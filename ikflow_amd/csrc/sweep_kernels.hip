@@ -19,6 +19,11 @@
 // table (the start edge's key frame 0 once), every lane reads it as a broadcast like the static table, the lanes that are still undecided test
 // the sample (track_sample_blocked, track_math.h), and the wave leaves the sample loop when every lane is decided.  TRACK = false is the kernel
 // as it was, instruction for instruction (profiles/sweep_kernel_resources.txt).
+//
+// BATCH (the lattice source over P paths in one layout of P T waypoints, include/ikflow_amd_path_batch.h; taken only by the batch entries): a
+// wave's waypoint g of the layout gives its path p = g / T and its waypoint t = g % T inside it (path_batch_math.h).  t == 0 is the start edge
+// of path p, from q_start[p]; otherwise the predecessor row is j P T + g - 1.  The mask is sweep_word_index over P T waypoints, so wave = word
+// as before.  Never together with TRACK.  BATCH = false is the kernel as it was.
 #include "ikf_internal.h"
 
 namespace ikf {
@@ -31,8 +36,9 @@ static_assert(kSweepTrackMaxLds == 4096 + 4096 + 37120, "obstacle table + one fi
 static_assert(kSweepTrackMaxLds <= 48 * 1024, "a tracked sweep workgroup fits the dynamic LDS that needs no opt-in");
 constexpr long long kSweepMaxGrid = 1LL << 20;
 
-template <int NDOF, bool TRACK>
+template <int NDOF, bool TRACK, bool BATCH>
 __global__ __launch_bounds__(IKF_SWEEP_LANES) void k_sweep_edges(const SweepArgs a) {
+  static_assert(!(TRACK && BATCH), "a world track has one frame per waypoint of ONE path");
   extern __shared__ float sweep_lds[];   // [n_obs x 16] obstacle table, then [64][cap_stride] capsule end points
   const int lane = threadIdx.x;
   const int n_obs = a.n_obs;
@@ -46,7 +52,8 @@ __global__ __launch_bounds__(IKF_SWEEP_LANES) void k_sweep_edges(const SweepArgs
   const bool lattice = a.lattice != 0;
   const long long T = a.T;
   const int k = a.k;
-  const long long n_waves = lattice ? sweep_mask_words(T, k) : sweep_pair_waves(a.n);
+  const long long G = BATCH ? path_batch_waypoints(a.P, T) : T;   // waypoints of the layout: the row stride of q and node
+  const long long n_waves = lattice ? sweep_mask_words(G, k) : sweep_pair_waves(a.n);
   for (long long wave = blockIdx.x; wave < n_waves; wave += gridDim.x) {
     float ea[NDOF], eb[NDOF];
 #pragma unroll
@@ -54,20 +61,27 @@ __global__ __launch_bounds__(IKF_SWEEP_LANES) void k_sweep_edges(const SweepArgs
     bool active = false, all_free = false;
     const long long i = wave * IKF_SWEEP_LANES + lane;   // pair source: the lane's edge
     if (lattice) {
-      long long t;
+      long long g, t;   // the wave's waypoint in the layout, and inside its path (the same without a batch)
       int r, word;
-      sweep_wave_role(wave, k, &t, &r, &word);
+      sweep_wave_role(wave, k, &g, &r, &word);
+      t = g;
+      const float* q_start = a.q_start;
+      if constexpr (BATCH) {   // t == 0 is the start edge of path p: nothing joins it to the last waypoint of path p - 1
+        const PathBatchRole role = path_batch_role(g, T);
+        t = role.t;
+        if (q_start) q_start += role.p * NDOF;
+      }
       const int j = word * IKF_SWEEP_LANES + lane;
-      const bool dest_ok = a.node[(long long)r * T + t] < rank_inf();
+      const bool dest_ok = a.node[(long long)r * G + g] < rank_inf();
       const float* pa = nullptr;
       if (t == 0) {
-        all_free = a.q_start == nullptr;
-        if (a.q_start && j == 0 && dest_ok) pa = a.q_start;
-      } else if (j < k && dest_ok && a.node[(long long)j * T + t - 1] < rank_inf()) {
-        pa = a.q + ((long long)j * T + t - 1) * NDOF;
+        all_free = q_start == nullptr;
+        if (q_start && j == 0 && dest_ok) pa = q_start;
+      } else if (j < k && dest_ok && a.node[(long long)j * G + g - 1] < rank_inf()) {
+        pa = a.q + ((long long)j * G + g - 1) * NDOF;
       }
       if (pa) {
-        const float* const pb = a.q + ((long long)r * T + t) * NDOF;
+        const float* const pb = a.q + ((long long)r * G + g) * NDOF;
         active = true;
 #pragma unroll
         for (int d = 0; d < NDOF; ++d) {
@@ -124,8 +138,10 @@ hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
   long long waves;
   if (a.lattice) {
-    if (a.T < 1 || a.k < 1 || a.k > IKF_PATH_MAX_K || (long long)a.k * a.T > 0x7fffffffLL || !a.q || !a.node || !a.edge_free) return hipErrorInvalidValue;
-    waves = sweep_mask_words(a.T, a.k);
+    const long long paths = a.P > 0 ? a.P : 1;
+    if (a.T < 1 || a.k < 1 || a.k > IKF_PATH_MAX_K || a.P < 0 || (long long)a.k * a.T * paths > 0x7fffffffLL || !a.q || !a.node || !a.edge_free)
+      return hipErrorInvalidValue;
+    waves = sweep_mask_words(a.T * paths, a.k);
   } else {
     if (a.n <= 0) return hipSuccess;
     if (!a.qa || !a.qb || (!a.blocked_out && !a.first_out)) return hipErrorInvalidValue;
@@ -136,10 +152,14 @@ hipError_t launch_sweep_edges(int ndof, const SweepArgs& a, hipStream_t s) {
   const size_t lds = sizeof(float) * (((size_t)a.n_obs + (track ? a.n_track : 0)) * IKF_WORLD_OBSTACLE_WORDS +
                                       IKF_SWEEP_LANES * (size_t)((a.n_caps * 6) | 1));
   const unsigned grid = (unsigned)(waves < kSweepMaxGrid ? waves : kSweepMaxGrid);
+  const bool batch = a.lattice && a.P > 0;
+  if (track && batch) return hipErrorInvalidValue;   // frames per batched path: not covered (include/ikflow_amd_path_batch.h)
   if (track) {
-    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND, true>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
+    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND, true, false>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
+  } else if (batch) {
+    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND, false, true>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
   } else {
-    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND, false>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
+    IKF_NDOF_DISPATCH(ndof, hipLaunchKernelGGL((k_sweep_edges<ND, false, false>), dim3(grid), dim3(IKF_SWEEP_LANES), lds, s, a));
   }
   return hipGetLastError();
 }

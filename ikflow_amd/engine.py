@@ -751,6 +751,57 @@ class Engine:
                 None if q_start is None else q_start.data_ptr(), C.byref(opt), *[None if t is None else t.data_ptr() for t in outs], self._stream()))
         return outs
 
+    # -- path IK, P paths per call (include/ikflow_amd_path_batch.h) ---------------------------------------
+    def reserve_path_batch(self, max_paths: int, max_waypoints: int, max_k: int) -> None:
+        """Pre-size what generate_paths needs for up to max_paths x max_waypoints x max_k candidates, so that later calls allocate nothing."""
+        self._ck(self.lib.ikf_reserve_path_batch(self._h, int(max_paths), int(max_waypoints), int(max_k)))
+
+    def _path_batch_inputs(self, waypoints: torch.Tensor, k: int, rows: torch.Tensor, shared: bool, cols: int, q_start: Optional[torch.Tensor], what: str):
+        wp = self._on_device(waypoints, "waypoints")
+        assert wp.ndim == 3 and wp.shape[2] == 7, f"waypoints must be of shape [P x T x 7], got {tuple(wp.shape)}"
+        assert 1 <= k <= _lib.IKF_PATH_MAX_K, f"k must be in 1 .. {_lib.IKF_PATH_MAX_K}, got {k}"
+        P, T = wp.shape[0], wp.shape[1]
+        rows = self._on_device(rows, what)
+        n_rows = k if shared else k * P * T
+        assert rows.ndim == 2 and rows.shape == (n_rows, cols), f"{what} must be [{n_rows} x {cols}], got {tuple(rows.shape)}"
+        if q_start is not None:
+            q_start = self._on_device(q_start, "q_start")
+            assert q_start.shape == (P, self.layout.ndof), f"q_start must be [{P} x {self.layout.ndof}], got {tuple(q_start.shape)}"
+        return wp, P, T, rows, q_start
+
+    def _path_batch_outputs(self, P: int, T: int, k: int, node_costs: bool):
+        paths = torch.empty((P, T, self.layout.ndof), dtype=torch.float32, device=self.device)
+        index = torch.empty((P, T), dtype=torch.int32, device=self.device)
+        cost = torch.full((P,), float("inf"), dtype=torch.float32, device=self.device)   # (T = 0: the call writes nothing)
+        reach = torch.empty((P, T), dtype=torch.int32, device=self.device)
+        nodes = torch.empty((k, P, T), dtype=torch.float32, device=self.device) if node_costs else None
+        return paths, index, cost, reach, nodes
+
+    def path_search_batch(self, waypoints: torch.Tensor, k: int, q: torch.Tensor, opt, q_start: Optional[torch.Tensor] = None,
+                          node_costs: bool = False):
+        """waypoints [P x T x 7]; q [k * P * T x ndof] (row r * (P * T) + p * T + t = candidate r of waypoint t of path p); q_start [P x ndof];
+        opt: path_options(...).  Path p is path_search on its own lattice
+        -> (paths [P x T x ndof], index [P x T] int32, cost [P], n_reachable [P x T] int32, node_costs [k x P x T] or None)."""
+        wp, P, T, q, q_start = self._path_batch_inputs(waypoints, k, q, False, self.layout.ndof, q_start, "q")
+        outs = self._path_batch_outputs(P, T, k, node_costs)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_path_search_batch(
+                self._h, wp.data_ptr(), P, T, int(k), q.data_ptr(), None if q_start is None else q_start.data_ptr(), C.byref(opt),
+                *[None if t is None else t.data_ptr() for t in outs], self._stream()))
+        return outs
+
+    def generate_paths(self, waypoints: torch.Tensor, k: int, latent: torch.Tensor, shared_latent: bool, clamp: bool, opt,
+                       q_start: Optional[torch.Tensor] = None, node_costs: bool = False):
+        """The flow on k candidates per waypoint of P paths - latent [k x D] held fixed along every path (shared_latent), or [k * P * T x D] in
+        the candidate layout - and the P searches through them, without a host round trip in between; same outputs as path_search_batch."""
+        wp, P, T, latent, q_start = self._path_batch_inputs(waypoints, k, latent, bool(shared_latent), self.layout.dim, q_start, "latent")
+        outs = self._path_batch_outputs(P, T, k, node_costs)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_generate_path_batch(
+                self._h, wp.data_ptr(), P, T, int(k), latent.data_ptr(), 1 if shared_latent else 0, 1 if clamp else 0,
+                None if q_start is None else q_start.data_ptr(), C.byref(opt), *[None if t is None else t.data_ptr() for t in outs], self._stream()))
+        return outs
+
     # -- diverse-of-K IK (include/ikflow_amd_diverse.h) ---------------------------------------------------
     def reserve_diverse(self, max_poses: int, max_k: int) -> None:
         """Pre-size what generate_diverse needs for up to max_poses x max_k candidates, so that later calls allocate nothing."""

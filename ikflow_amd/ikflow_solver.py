@@ -72,6 +72,22 @@ class PathSolution4(NamedTuple):
     n_reachable: torch.Tensor
 
 
+class PathsSolution(NamedTuple):
+    """What generate_ik_paths returns (node_costs only with return_node_costs=True, else the 4-tuple PathsSolution4)."""
+    paths: torch.Tensor          # [P x T x ndof]; a path that does not exist is all 0
+    index: torch.Tensor          # [P x T] int32, the candidate chosen per waypoint; -1 along a path that does not exist
+    cost: torch.Tensor           # [P] the totals of the lattices; +inf where there is no path
+    n_reachable: torch.Tensor    # [P x T] int32, candidates of a waypoint that some admissible path of its lattice reaches
+    node_costs: torch.Tensor     # [k x P x T]; +inf for an inadmissible candidate
+
+
+class PathsSolution4(NamedTuple):
+    paths: torch.Tensor
+    index: torch.Tensor
+    cost: torch.Tensor
+    n_reachable: torch.Tensor
+
+
 class DiverseSolutions(NamedTuple):
     """What generate_diverse_ik_solutions returns (row_scores only with return_row_scores=True, else the 6-tuple DiverseSolutions6)."""
     solutions: torch.Tensor      # [m x n_keep x ndof]; unfilled slots are 0
@@ -728,6 +744,73 @@ class IKFlowSolver:
         if return_node_costs:
             return PathSolution(path, index, cost, reach, nodes)
         return PathSolution4(path, index, cost, reach)
+
+    # -- many joint-space paths per call ------------------------------------------------------------------------------
+    def generate_ik_paths(
+        self,
+        waypoints: torch.Tensor,
+        k: int,
+        latent: Optional[torch.Tensor] = None,
+        shared_latent: bool = True,
+        latent_distribution: str = "gaussian",
+        latent_scale: float = 1.0,
+        clamp_to_joint_limits: bool = True,
+        rot_weight: float = mm_to_m(1) / 0.1,
+        node_weight: float = 1.0,
+        max_joint_step: Optional[float] = None,
+        q_start: Optional[torch.Tensor] = None,
+        pos_error_threshold: Optional[float] = None,
+        rot_error_threshold: Optional[float] = None,
+        reject_joint_limits: bool = True,
+        reject_self_collisions: Optional[bool] = None,
+        min_clearance: float = 0.0,
+        refine_steps: int = 0,
+        return_node_costs: bool = False,
+    ):
+        """generate_ik_path for P pose sequences of T waypoints each in ONE call - one flow call on all P * T * k candidates and the P searches
+        side by side on the GPU (include/ikflow_amd_path_batch.h).  Path p is what generate_ik_path returns for ``waypoints[p]`` with
+        ``q_start[p]`` on the same candidates; nothing joins one path to the next.
+
+        waypoints: [P x T x 7].  With shared_latent (the default) the latent is drawn as ``draw_latent(..., (k, dim))`` and candidate r uses
+        latent r at every waypoint of every path; otherwise as ``(k * P * T, dim)``, row r * (P * T) + p * T + t for candidate r of waypoint t
+        of path p.  q_start: [P x ndof] or None.  Every other argument, and what is set on the solver (world, cloud, manipulability floor,
+        candidate refinement, sweep), is generate_ik_path's and applies to every path; a world track set by set_world_track is refused.
+
+        refine_steps > 0 applies that many Levenberg-Marquardt steps to the rows of the paths that exist (finite cost); the others stay 0.
+
+        Returns the named tuple (paths [P x T x ndof], index [P x T] int32, cost [P], n_reachable [P x T] int32[, node_costs [k x P x T]]);
+        a path that does not exist: rows 0, indices -1, cost +inf."""
+        assert isinstance(waypoints, torch.Tensor), f"waypoints must be a torch.Tensor (got {type(waypoints)})."
+        assert waypoints.ndim == 3 and waypoints.shape[2] == 7, f"waypoints must be of shape [P x T x 7], got {tuple(waypoints.shape)}"
+        P, T = waypoints.shape[0], waypoints.shape[1]
+        # (the method's own asserts come first: the shared ones end with the device check, which a CPU tensor on a GPU machine does not pass)
+        assert isinstance(refine_steps, int) and refine_steps >= 0, f"refine_steps must be an int >= 0, got {refine_steps!r}"
+        assert q_start is None or (isinstance(q_start, torch.Tensor) and tuple(q_start.shape) == (P, self.ndof)), (
+            f"q_start must be [{P} x {self.ndof}], got {tuple(q_start.shape) if isinstance(q_start, torch.Tensor) else type(q_start)}")
+        assert node_weight >= 0, f"node_weight must be >= 0, got {node_weight!r}"
+        assert max_joint_step is None or max_joint_step >= 0, "max_joint_step must be None (no gate) or >= 0"
+        flat, n, n_latent, reject_self_collisions = self._candidate_args(
+            waypoints.reshape(P * T, 7), "waypoints", "P * T", k, 256, latent, shared_latent, latent_distribution, latent_scale,
+            reject_self_collisions, pos_error_threshold, rot_error_threshold)
+
+        with torch.inference_mode():
+            eng, latent = self._candidate_engine(waypoints.device, reject_self_collisions, latent, latent_distribution, latent_scale, n_latent)
+            opt = eng.path_options(rot_weight, pos_error_threshold, rot_error_threshold, reject_joint_limits, reject_self_collisions,
+                                   min_clearance, node_weight, max_joint_step)
+            paths, index, cost, reach, nodes = eng.generate_paths(waypoints, k, latent, shared_latent, clamp_to_joint_limits, opt,
+                                                                  q_start=q_start, node_costs=return_node_costs)
+            if refine_steps > 0 and n > 0:
+                found = torch.isfinite(cost)
+                if bool(found.any().item()):   # only the paths that exist: a no-path entry stays at zeros
+                    targets = waypoints[found].reshape(-1, 7)
+                    rows = paths[found].reshape(-1, self.ndof)
+                    for _ in range(refine_steps):
+                        rows = eng.lm_step(targets, rows)
+                    paths = paths.clone()
+                    paths[found] = rows.reshape(-1, T, self.ndof)
+        if return_node_costs:
+            return PathsSolution(paths, index, cost, reach, nodes)
+        return PathsSolution4(paths, index, cost, reach)
 
     # -- log-likelihood (forward pass) ----------------------------------------------------------------------
     def _forward_inputs(self, solutions: torch.Tensor, target_poses: torch.Tensor, pad: Optional[torch.Tensor]):
