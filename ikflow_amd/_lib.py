@@ -243,6 +243,25 @@ PATH_BATCH_SIGNATURES = {
     "ikf_reserve_path_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
 }
 
+# ... every symbol include/ikflow_amd_path_opt.h declares (path IK, third stage: a least-squares pass over whole paths behind the lattice)
+IKF_PATH_OPT_MAX_ITERS = 32
+PATH_OPT_REASONS = {0: "committed", 1: "no step lowered F", 2: "node inadmissible", 3: "edge forbidden", 4: "cost not lower"}
+PATH_OPT_SIGNATURES = {
+    # waypoints, P, T, path_in, q_start, opt, n_iters, smooth_weight, validate, path_out, cost_out, info_out, stream
+    "ikf_path_optimize": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ikf_path_options), C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
+    # waypoints, P, T, path, q_start, opt, cost_out, info_out, stream
+    "ikf_path_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ikf_path_options), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ikf_set_path_optimize": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "ikf_get_path_optimize": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    # P, h_info [P x 4]
+    "ikf_path_optimize_info": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
+    "ikf_reserve_path_opt": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+}
+
 # ... every symbol include/ikflow_amd_diverse.h declares (diverse-of-K IK: a far-apart set of each pose's admissible candidates)
 # q_out, score_out, index_out, separation_out, kept_out, count_out, row_score_out
 _DIVERSE_OUTPUTS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -350,7 +369,7 @@ def load(flavour: str = "") -> C.CDLL:
     import torch  # noqa: F401
 
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(PATH_BATCH_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(MANIP_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RANK_SIGNATURES.items()) + list(PATH_SIGNATURES.items()) + list(PATH_BATCH_SIGNATURES.items()) + list(PATH_OPT_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(WORLD_SIGNATURES.items()) + list(CLOUD_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + list(REFINE_SIGNATURES.items()) + list(EXACT_WORLD_SIGNATURES.items()) + list(TRACK_SIGNATURES.items()) + list(MANIP_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -16,9 +16,9 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libikflow_amd.so")
 PROBES_LIB_PATH = os.path.join(LIB_DIR, "libikflow_amd_probes.so")
-SOURCES = ["flow_kernels.hip", "flow_fused.hip", "flow_rowowner.hip", "flow_split.hip", "flow_forward.hip", "flow_inverse.hip", "kin_kernels.hip", "rank_kernels.hip", "api_handle.hip", "api_weights.hip", "api_flow.hip", "api_kin.hip", "api_rank.hip", "path_kernels.hip", "api_path.hip", "diverse_kernels.hip", "api_diverse.hip", "world_kernels.hip", "api_world.hip", "cloud_kernels.hip", "api_cloud.hip", "sweep_kernels.hip", "api_sweep.hip", "refine_kernels.hip", "api_refine.hip", "exact_world_kernels.hip", "api_exact_world.hip", "track_kernels.hip", "api_track.hip", "manip_kernels.hip", "api_manip.hip"]
-HEADERS = [os.path.join(CSRC, "ikf_internal.h"), os.path.join(CSRC, "ikf_model.h"), os.path.join(CSRC, "device_buf.h"), os.path.join(CSRC, "flow_plan.h"), os.path.join(CSRC, "flow_math.h"), os.path.join(CSRC, "kin_math.h"), os.path.join(CSRC, "rank_math.h"), os.path.join(CSRC, "path_math.h"), os.path.join(CSRC, "path_batch_math.h"), os.path.join(CSRC, "diverse_math.h"), os.path.join(CSRC, "world_math.h"), os.path.join(CSRC, "cloud_math.h"), os.path.join(CSRC, "sweep_math.h"), os.path.join(CSRC, "refine_math.h"), os.path.join(CSRC, "exact_world_math.h"), os.path.join(CSRC, "track_math.h"), os.path.join(CSRC, "manip_math.h"), os.path.join(CSRC, "flow_split_dma.inc"), os.path.join(CSRC, "flow_fused_probes.inc"), os.path.join(_HERE, "..", "include", "ikflow_amd.h"),
-           os.path.join(_HERE, "..", "include", "ikflow_amd_debug.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_rank.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_path.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_path_batch.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_diverse.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_world.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_cloud.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_sweep.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_refine.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_exact_world.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_track.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_manip.h")]
+SOURCES = ["flow_kernels.hip", "flow_fused.hip", "flow_rowowner.hip", "flow_split.hip", "flow_forward.hip", "flow_inverse.hip", "kin_kernels.hip", "rank_kernels.hip", "api_handle.hip", "api_weights.hip", "api_flow.hip", "api_kin.hip", "api_rank.hip", "path_kernels.hip", "api_path.hip", "path_opt_kernels.hip", "api_path_opt.hip", "diverse_kernels.hip", "api_diverse.hip", "world_kernels.hip", "api_world.hip", "cloud_kernels.hip", "api_cloud.hip", "sweep_kernels.hip", "api_sweep.hip", "refine_kernels.hip", "api_refine.hip", "exact_world_kernels.hip", "api_exact_world.hip", "track_kernels.hip", "api_track.hip", "manip_kernels.hip", "api_manip.hip"]
+HEADERS = [os.path.join(CSRC, "ikf_internal.h"), os.path.join(CSRC, "ikf_model.h"), os.path.join(CSRC, "device_buf.h"), os.path.join(CSRC, "flow_plan.h"), os.path.join(CSRC, "flow_math.h"), os.path.join(CSRC, "kin_math.h"), os.path.join(CSRC, "rank_math.h"), os.path.join(CSRC, "path_math.h"), os.path.join(CSRC, "path_batch_math.h"), os.path.join(CSRC, "path_opt_math.h"), os.path.join(CSRC, "diverse_math.h"), os.path.join(CSRC, "world_math.h"), os.path.join(CSRC, "cloud_math.h"), os.path.join(CSRC, "sweep_math.h"), os.path.join(CSRC, "refine_math.h"), os.path.join(CSRC, "exact_world_math.h"), os.path.join(CSRC, "track_math.h"), os.path.join(CSRC, "manip_math.h"), os.path.join(CSRC, "flow_split_dma.inc"), os.path.join(CSRC, "flow_fused_probes.inc"), os.path.join(_HERE, "..", "include", "ikflow_amd.h"),
+           os.path.join(_HERE, "..", "include", "ikflow_amd_debug.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_rank.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_path.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_path_batch.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_path_opt.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_diverse.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_world.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_cloud.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_sweep.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_refine.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_exact_world.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_track.h"), os.path.join(_HERE, "..", "include", "ikflow_amd_manip.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 FLAGS += os.environ.get("IKF_HIPCC_FLAGS", "").split()  # probes only (e.g. -DIKF_NO_RANGE_FLAG); the shipped library is built without

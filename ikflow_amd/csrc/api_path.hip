@@ -15,11 +15,6 @@ static ikf_status ensure_path_mask(ikf_model* m, long long rows, int k) {
   IKF_HIP(m->pt_edge_free.ensure(rows * sweep_words(k)));
   return IKF_OK;
 }
-// A sweep is set (ikf_set_path_sweep) and there is something to test against: obstacles on the handle, a world track (include/ikflow_amd_track.h),
-// or the call rejects self-collisions.
-static bool path_sweeps(const ikf_model* m, const ikf_path_options* opt) {
-  return m->path_sweep > 0 && (m->world_n > 0 || m->track_F > 0 || opt->reject_collisions);
-}
 // the shared latent expanded to one row per candidate row
 static ikf_status ensure_path_latent(ikf_model* m, long long rows) {
   IKF_HIP(m->pt_latent.ensure(rows * m->dims.D));
@@ -89,6 +84,8 @@ static ikf_status run_path(ikf_model* m, const float* d_waypoints, int64_t P, in
   IKF_HIP(prof_mark(m, s));   // between ikf_profile_begin / _end the sequential stage is bracketed (tools/path_timing.py); otherwise nothing is recorded
   IKF_HIP(launch_path_lattice(m->dims.ndof, a, s));
   IKF_HIP(prof_mark(m, s));
+  // the path optimiser behind the lattice while it is set on the handle (include/ikflow_amd_path_opt.h): path_out and cost_out in place
+  if (m->popt_iters > 0) return path_opt_behind(m, d_waypoints, P > 0 ? P : 1, T, d_q_start, opt, d_path_out, d_cost_out, s);
   return IKF_OK;
 }
 
@@ -104,6 +101,7 @@ extern "C" ikf_status ikf_path_search(ikf_model* m, const float* d_waypoints, in
   IKF_ON_DEVICE(m)
   st = ensure_path_scratch(m, T * (long long)k);
   if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, T * (long long)k, k);
+  if (st == IKF_OK && m->popt_iters > 0) st = path_opt_ensure(m, 1, T, opt);
   if (st != IKF_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   StreamScope scope(m, s);
@@ -130,6 +128,7 @@ extern "C" ikf_status ikf_generate_path(ikf_model* m, const float* d_waypoints, 
   if (st == IKF_OK) st = ensure_path_scratch(m, rows);
   if (st == IKF_OK && shared_latent) st = ensure_path_latent(m, rows);
   if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, rows, k);
+  if (st == IKF_OK && m->popt_iters > 0) st = path_opt_ensure(m, 1, T, opt);
   if (st != IKF_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   StreamScope scope(m, s);
@@ -201,6 +200,7 @@ extern "C" ikf_status ikf_path_search_batch(ikf_model* m, const float* d_waypoin
   const long long rows = P * T * (long long)k;
   st = ensure_path_batch_scratch(m, P, T, k);
   if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, rows, k);
+  if (st == IKF_OK && m->popt_iters > 0) st = path_opt_ensure(m, P, T, opt);
   if (st != IKF_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   StreamScope scope(m, s);
@@ -226,6 +226,7 @@ extern "C" ikf_status ikf_generate_path_batch(ikf_model* m, const float* d_waypo
   if (st == IKF_OK) st = ensure_path_batch_scratch(m, P, T, k);
   if (st == IKF_OK && shared_latent) st = ensure_path_latent(m, rows);
   if (st == IKF_OK && path_sweeps(m, opt)) st = ensure_path_mask(m, rows, k);
+  if (st == IKF_OK && m->popt_iters > 0) st = path_opt_ensure(m, P, T, opt);
   if (st != IKF_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   StreamScope scope(m, s);

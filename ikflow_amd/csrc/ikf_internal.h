@@ -529,6 +529,43 @@ struct PathArgs {
 hipError_t launch_path_expand_latent(const float* latent, int k, long long T, int D, float* out, hipStream_t s);
 hipError_t launch_path_lattice(int ndof, const PathArgs& a, hipStream_t s);
 
+// path_opt_kernels.hip - the path optimiser (include/ikflow_amd_path_opt.h; the arithmetic: path_opt_math.h, included by that unit alone).  P >= 1
+// paths of T waypoints in the path-batch layout, a workgroup per path.
+struct PathOptArgs {
+  const Chain* ch;
+  const float* waypoints;     // [P * T][7]
+  const float* path_in;       // [P * T][ndof]
+  const float* q_start;       // [P][ndof], or null
+  const float* skip_cost;     // [P], or null: a path whose value is not below +inf (a lattice's "no path") is left alone, iters 0
+  int P, T, n_iters;
+  double w;                   // smooth_weight
+  float* q;                   // [P * T][ndof] the iterate: the optimiser's result
+  float* q_prev;              // [P * T][ndof] the previous iterate
+  double* work;               // [P * T][path_opt_wp_doubles(ndof)]
+  int* iters_out;             // [P] steps kept
+};
+hipError_t launch_path_opt(int ndof, const PathOptArgs& a, hipStream_t s);
+// The evaluator's fold and the commit rule.  path_opt null: the evaluator as a query on path_in (node_in / edge_in), path_out may be null.
+struct PathOptCommitArgs {
+  const float* path_in;       // [P * T][ndof]
+  const float* path_opt;      // [P * T][ndof] the optimiser's iterate, or null
+  const float* q_start;       // [P][ndof], or null
+  const float* node_in;       // [P * T] k = 1 row scores of path_in (read when validate, or as a query)
+  const uint64_t* edge_in;    // [P * T] words of the k = 1 lattice mask of path_in, or null: no sweep
+  const float* node_opt;      // the same of path_opt
+  const uint64_t* edge_opt;
+  const int* iters;           // [P] of launch_path_opt
+  const float* skip_cost;     // as PathOptArgs (may be cost_out)
+  int P, T;
+  float node_weight, max_joint_step;
+  int validate;
+  float* path_out;            // [P * T][ndof]; may be path_in
+  float* cost_out;            // [P]
+  int* info_out;              // [P][4], or null
+  int* info_keep;             // [P][4] the handle's copy
+};
+hipError_t launch_path_opt_commit(int ndof, const PathOptCommitArgs& a, hipStream_t s);
+
 // diverse_kernels.hip - diverse-of-K IK (include/ikflow_amd_diverse.h; the arithmetic: diverse_math.h)
 struct DiverseArgs {
   const float* q;             // [k * n][ndof] tile-major candidates

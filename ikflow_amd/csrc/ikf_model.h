@@ -195,6 +195,16 @@ struct ikf_model {
   std::vector<WorldObstacle> track_fine;   // [track_fine_frames(track_F, track_S)][track_n]
   DeviceBuf<WorldObstacle> d_track;        // the same on the device
   DeviceBuf<float> tk_zero_node;           // [rows]
+  // path optimiser (api_path_opt.hip, api_path.hip): steps behind every lattice (0: off) and their smooth_weight; the iterate, the previous iterate
+  // and the per-waypoint fp64 scratch of k_path_opt; the k = 1 node scores and mask words of the input and of the optimised path, the ranking
+  // kernel's kept rows (not used), the steps kept and the info words of the last optimising call
+  int popt_iters = 0;
+  float popt_weight = 0.f;
+  DeviceBuf<float> po_q, po_prev, po_keep, po_node_in, po_node_opt;
+  DeviceBuf<double> po_work;
+  DeviceBuf<uint64_t> po_edge_in, po_edge_opt;
+  DeviceBuf<int> po_iters, po_info;
+  long long po_info_paths = 0;   // paths of the last optimising call (ikf_path_optimize_info)
   // refined candidates (api_refine.hip, api_rank.hip): LM steps on the flow's candidate rows before they are scored (0: none) and their tolerances
   int refine_steps = 0;
   float refine_pos_tol = 0.f, refine_rot_tol = 0.f;
@@ -290,6 +300,12 @@ struct StreamScope {
   StreamScope& operator=(const StreamScope&) = delete;
 };
 
+// A sweep is set (ikf_set_path_sweep) and there is something to test against: obstacles on the handle, a world track (include/ikflow_amd_track.h),
+// or the call rejects self-collisions.  (api_path.hip, api_path_opt.hip)
+static inline bool path_sweeps(const ikf_model* m, const ikf_path_options* opt) {
+  return m->path_sweep > 0 && (m->world_n > 0 || m->track_F > 0 || opt->reject_collisions);
+}
+
 static const long long kMaxChunkRows = 16384;  // keeps the [chunk x width] activations (64 MB each at width 1024) inside the 256 MB L3
 // The kernels tile the hidden width in units of 256.  Any other coeff_fn_internal_size (ikflow/model.py:51-96 accepts any)
 // is run at the next multiple of 256 with zero weights and biases in the padding: a padded unit outputs lrelu(0) = 0 and
@@ -354,6 +370,12 @@ ikf_status run_cloud_clearance(ikf_model* m, const float* d_q, long long rows, f
 // (nothing without a track; ikf_set_path_sweep calls it BEFORE it takes S - a refused blend reports frame and obstacle and leaves the table as
 // it was).  track_check_T: T <= F while a track is set.  track_mask_nodes: the node sink of k_track_clearance on a path call's node costs
 // (nothing without a track).  track_fill_sweep: the track's fields of a lattice SweepArgs (nothing without a track).
+// The path optimiser behind a lattice (api_path_opt.hip; called by api_path.hip while ikf_set_path_optimize is set).  path_opt_ensure: the scratch
+// of P x T, before the stream scope.  path_opt_behind: optimise d_path in place with validate = 1 on the caller's stream, inside its scope; d_cost
+// [P] is the lattice's cost on entry (+inf: the path is left alone) and the committed path's on exit.
+ikf_status path_opt_ensure(ikf_model* m, long long P, long long T, const ikf_path_options* opt);
+ikf_status path_opt_behind(ikf_model* m, const float* d_waypoints, long long P, long long T, const float* d_q_start, const ikf_path_options* opt,
+                           float* d_path, float* d_cost, hipStream_t s);
 ikf_status track_rebuild(ikf_model* m, const std::string& who, int S);
 ikf_status track_check_T(const ikf_model* m, const std::string& who, int64_t T);
 ikf_status track_mask_nodes(ikf_model* m, const float* d_q, int64_t T, int k, float* d_node, hipStream_t s);

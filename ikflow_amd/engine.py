@@ -802,6 +802,64 @@ class Engine:
                 None if q_start is None else q_start.data_ptr(), C.byref(opt), *[None if t is None else t.data_ptr() for t in outs], self._stream()))
         return outs
 
+    # -- path IK, third stage: the path optimiser (include/ikflow_amd_path_opt.h) ---------------------------
+    def reserve_path_opt(self, max_paths: int, max_waypoints: int) -> None:
+        """Pre-size what path_optimize / path_cost need for up to max_paths x max_waypoints, so that later calls allocate nothing."""
+        self._ck(self.lib.ikf_reserve_path_opt(self._h, int(max_paths), int(max_waypoints)))
+
+    def set_path_optimize(self, n_iters: int, smooth_weight: float = 0.0) -> None:
+        """n_iters > 0: path_search, generate_path and their batch forms run the optimiser (validate = 1) behind the lattice.  0: off (the default)."""
+        self._ck(self.lib.ikf_set_path_optimize(self._h, int(n_iters), float(smooth_weight)))
+
+    def path_optimize_state(self) -> Tuple[int, float]:
+        n, w = C.c_int(0), C.c_float(0.0)
+        self._ck(self.lib.ikf_get_path_optimize(self._h, C.byref(n), C.byref(w)))
+        return n.value, w.value
+
+    def _path_opt_inputs(self, waypoints: torch.Tensor, path: torch.Tensor, q_start: Optional[torch.Tensor]):
+        wp = self._on_device(waypoints, "waypoints")
+        assert wp.ndim == 3 and wp.shape[2] == 7, f"waypoints must be of shape [P x T x 7], got {tuple(wp.shape)}"
+        P, T = wp.shape[0], wp.shape[1]
+        path = self._on_device(path, "path")
+        assert path.shape == (P, T, self.layout.ndof), f"path must be [{P} x {T} x {self.layout.ndof}], got {tuple(path.shape)}"
+        if q_start is not None:
+            q_start = self._on_device(q_start, "q_start")
+            assert q_start.shape == (P, self.layout.ndof), f"q_start must be [{P} x {self.layout.ndof}], got {tuple(q_start.shape)}"
+        return wp, P, T, path, q_start
+
+    def path_optimize(self, waypoints: torch.Tensor, path: torch.Tensor, opt, n_iters: int, smooth_weight: float, validate: bool = True,
+                      q_start: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+        """waypoints [P x T x 7]; path [P x T x ndof]; q_start [P x ndof]; opt: path_options(...); out: where the result goes (may be `path`)
+        -> (paths [P x T x ndof], cost [P], info [P x 4] int32 = iters, committed, reason, where)."""
+        wp, P, T, path, q_start = self._path_opt_inputs(waypoints, path, q_start)
+        if out is None:
+            out = torch.empty_like(path)
+        assert out.is_contiguous() and out.shape == path.shape and out.dtype == torch.float32 and out.device == path.device, "out must be like path"
+        cost = torch.full((P,), float("inf"), dtype=torch.float32, device=self.device)   # (P * T = 0: the call writes nothing)
+        info = torch.zeros((P, 4), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_path_optimize(
+                self._h, wp.data_ptr(), P, T, path.data_ptr(), None if q_start is None else q_start.data_ptr(), C.byref(opt), int(n_iters),
+                float(smooth_weight), 1 if validate else 0, out.data_ptr(), cost.data_ptr(), info.data_ptr(), self._stream()))
+        return out, cost, info
+
+    def path_cost(self, waypoints: torch.Tensor, path: torch.Tensor, opt, q_start: Optional[torch.Tensor] = None):
+        """The evaluator alone: the lattice's cost of one row per waypoint -> (cost [P], info [P x 4] int32 = 0, admissible, reason, where)."""
+        wp, P, T, path, q_start = self._path_opt_inputs(waypoints, path, q_start)
+        cost = torch.full((P,), float("inf"), dtype=torch.float32, device=self.device)
+        info = torch.zeros((P, 4), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_path_cost(self._h, wp.data_ptr(), P, T, path.data_ptr(), None if q_start is None else q_start.data_ptr(), C.byref(opt),
+                                            cost.data_ptr(), info.data_ptr(), self._stream()))
+        return cost, info
+
+    def path_optimize_info(self, n_paths: int) -> np.ndarray:
+        """[n_paths x 4] int32 info words of the handle's last optimising call (waits for it)."""
+        out = np.zeros((int(n_paths), 4), np.int32)
+        with torch.cuda.device(self.device):
+            self._ck(self.lib.ikf_path_optimize_info(self._h, int(n_paths), out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
     # -- diverse-of-K IK (include/ikflow_amd_diverse.h) ---------------------------------------------------
     def reserve_diverse(self, max_poses: int, max_k: int) -> None:
         """Pre-size what generate_diverse needs for up to max_poses x max_k candidates, so that later calls allocate nothing."""

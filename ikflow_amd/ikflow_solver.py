@@ -88,6 +88,14 @@ class PathsSolution4(NamedTuple):
     n_reachable: torch.Tensor
 
 
+class PathOptimization(NamedTuple):
+    """One path's entry of last_path_optimization() (include/ikflow_amd_path_opt.h)."""
+    iters: int                   # steps kept
+    committed: bool              # the optimised path was returned
+    reason: str                  # "committed", "no step lowered F", "node inadmissible", "edge forbidden", "cost not lower"
+    where: int                   # the first offending waypoint (for an edge: the waypoint it ends at), or -1
+
+
 class DiverseSolutions(NamedTuple):
     """What generate_diverse_ik_solutions returns (row_scores only with return_row_scores=True, else the 6-tuple DiverseSolutions6)."""
     solutions: torch.Tensor      # [m x n_keep x ndof]; unfilled slots are 0
@@ -148,6 +156,8 @@ class IKFlowSolver:
         self._world = None   # (World, min_clearance) of set_world: re-applied to every engine this solver creates
         self._world_cloud = None  # (points [n x 3] host f32, point_radius, min_clearance) of set_world_cloud: likewise
         self._path_sweep = 0  # samples per lattice edge of set_path_sweep: likewise
+        self._last_path_opt_paths = None  # paths of the last call that ran the path optimiser (last_path_optimization)
+        self._path_optimization = (0, 0.0)  # (n_iters, smooth_weight) of set_path_optimization: likewise
         self._world_track = None  # (worlds, min_clearance) of set_world_track: likewise (pushed after the collision model, the world and the sweep)
         self._candidate_refine = (0, 0.0, 0.0)  # (n_steps, pos_tol, rot_tol) of set_candidate_refine: likewise
         self._exact_collision = (False, False, 0.0)  # (enabled, reject_self_collisions, min_clearance) of set_exact_collision: likewise
@@ -208,6 +218,8 @@ class IKFlowSolver:
                 self._push_world_track(eng)
             if self._candidate_refine[0]:
                 eng.set_candidate_refine(*self._candidate_refine)
+            if self._path_optimization[0]:
+                eng.set_path_optimize(*self._path_optimization)
             if self._min_manipulability[0]:
                 eng.set_min_manipulability(*self._min_manipulability)
             if self._exact_collision[0]:   # (after the collision model, the world and the cloud)
@@ -323,6 +335,88 @@ class IKFlowSolver:
         self._path_sweep = n_samples
         if self._engine is not None:
             self._engine.set_path_sweep(n_samples)
+
+    def set_path_optimization(self, n_iters: int, smooth_weight: float):
+        """A least-squares pass over the whole path behind the lattice of generate_ik_path / generate_ik_paths (0 iterations: off, the default; at
+        most 32): up to n_iters damped Gauss-Newton steps on  sum_t |pose error_t|^2 + smooth_weight * sum_t |q_t - q_{t-1}|^2  (with q_start as
+        q_{-1}), all waypoints coupled, each step kept only if it lowers that sum (include/ikflow_amd_path_opt.h).  The optimised path is
+        returned only when every rule of the lattice admits it - thresholds, limits, self-collision, world, cloud, manipulability floor, world
+        track, step gate, sweep - and its cost BY THE LATTICE'S OWN COST is strictly lower; otherwise the lattice's path comes back unchanged.
+        ``index``, ``n_reachable`` and ``node_costs`` keep describing the lattice; ``cost`` is that of the returned path; last_path_optimization()
+        tells what happened.
+
+        smooth_weight has no default.  It is the ratio at which squared joint motion (rad^2 per waypoint) trades against squared pose error
+        (m^2 and rad^2): at smooth_weight = 1 a step of 0.03 rad between neighbours weighs as much as 3 cm of position error, at 0 every waypoint
+        is polished on its own (one fp64 LM step per iteration) and the motion between them is left as the lattice chose it.  The right value
+        depends on the waypoint spacing and on node_weight; none has been tuned here."""
+        assert isinstance(n_iters, int) and not isinstance(n_iters, bool) and 0 <= n_iters <= 32, f"n_iters must be an int in 0 .. 32, got {n_iters!r}"
+        assert isinstance(smooth_weight, (int, float)) and not isinstance(smooth_weight, bool) and math.isfinite(smooth_weight) and smooth_weight >= 0, (
+            f"smooth_weight must be a finite number >= 0, got {smooth_weight!r}")
+        self._path_optimization = (n_iters, float(smooth_weight)) if n_iters else (0, 0.0)
+        if self._engine is not None:
+            self._engine.set_path_optimize(*self._path_optimization)
+
+    def last_path_optimization(self):
+        """What the optimiser did in the last generate_ik_path / generate_ik_paths / optimize_ik_path call: one named tuple (iters, committed,
+        reason, where) per path - steps kept, whether the optimised path was returned, why not ("committed", "no step lowered F", "node
+        inadmissible", "edge forbidden", "cost not lower") and the first offending waypoint or -1.  None before any such call."""
+        if self._engine is None or self._last_path_opt_paths is None:
+            return None
+        from ikflow_amd import _lib
+
+        info = self._engine.path_optimize_info(self._last_path_opt_paths)
+        return [PathOptimization(int(r[0]), bool(r[1]), _lib.PATH_OPT_REASONS[int(r[2])], int(r[3])) for r in info]
+
+    def optimize_ik_path(
+        self,
+        waypoints: torch.Tensor,
+        path: torch.Tensor,
+        n_iters: int,
+        smooth_weight: float,
+        validate: bool = True,
+        rot_weight: float = mm_to_m(1) / 0.1,
+        node_weight: float = 1.0,
+        max_joint_step: Optional[float] = None,
+        q_start: Optional[torch.Tensor] = None,
+        pos_error_threshold: Optional[float] = None,
+        rot_error_threshold: Optional[float] = None,
+        reject_joint_limits: bool = True,
+        reject_self_collisions: Optional[bool] = None,
+        min_clearance: float = 0.0,
+    ):
+        """The optimiser of set_path_optimization on the caller's own path(s): waypoints [T x 7] with path [T x ndof] (q_start [ndof]), or
+        [P x T x 7] with [P x T x ndof] ([P x ndof]).  The rule keywords are generate_ik_path's and define the evaluator; with validate (the
+        default) the result is never a path those rules forbid nor one that costs more than the input.  Needs no weights.
+        Returns (path like the input, cost - a scalar for one path, [P] otherwise); last_path_optimization() has the details."""
+        assert isinstance(waypoints, torch.Tensor) and isinstance(path, torch.Tensor), "waypoints and path must be torch.Tensors"
+        single = waypoints.ndim == 2
+        assert waypoints.ndim in (2, 3) and waypoints.shape[-1] == 7, f"waypoints must be of shape [T x 7] or [P x T x 7], got {tuple(waypoints.shape)}"
+        assert tuple(path.shape) == tuple(waypoints.shape[:-1]) + (self.ndof,), (
+            f"path must be {list(waypoints.shape[:-1]) + [self.ndof]}, got {list(path.shape)}")
+        assert isinstance(n_iters, int) and not isinstance(n_iters, bool) and 1 <= n_iters <= 32, f"n_iters must be an int in 1 .. 32, got {n_iters!r}"
+        assert isinstance(smooth_weight, (int, float)) and not isinstance(smooth_weight, bool) and math.isfinite(smooth_weight) and smooth_weight >= 0, (
+            f"smooth_weight must be a finite number >= 0, got {smooth_weight!r}")
+        want = (self.ndof,) if single else (waypoints.shape[0], self.ndof)
+        assert q_start is None or (isinstance(q_start, torch.Tensor) and tuple(q_start.shape) == want), f"q_start must be {list(want)}"
+        assert node_weight >= 0, f"node_weight must be >= 0, got {node_weight!r}"
+        assert max_joint_step is None or max_joint_step >= 0, "max_joint_step must be None (no gate) or >= 0"
+        assert pos_error_threshold is None or pos_error_threshold >= 0, "pos_error_threshold must be None (no bound) or >= 0"
+        assert rot_error_threshold is None or rot_error_threshold >= 0, "rot_error_threshold must be None (no bound) or >= 0"
+        if reject_self_collisions is None:
+            reject_self_collisions = self._robot.has_collision_model
+        assert not reject_self_collisions or self._robot.has_collision_model, "reject_self_collisions needs a collision model (Robot.set_collision_capsules)"
+        with torch.inference_mode():
+            eng = self.engine(waypoints.device)
+            if reject_self_collisions and getattr(eng, "_collision_source", None) is not self._robot._collision_model:
+                eng.set_collision_model(*self._robot._collision_model)
+                eng._collision_source = self._robot._collision_model
+            opt = eng.path_options(rot_weight, pos_error_threshold, rot_error_threshold, reject_joint_limits, reject_self_collisions, min_clearance,
+                                   node_weight, max_joint_step)
+            wp3, path3 = (waypoints[None], path[None]) if single else (waypoints, path)
+            qs = None if q_start is None else (q_start[None] if single else q_start)
+            out, cost, _ = eng.path_optimize(wp3, path3, opt, n_iters, smooth_weight, validate=validate, q_start=qs)
+        self._last_path_opt_paths = wp3.shape[0] if wp3.shape[1] > 0 else 0
+        return (out[0], cost.reshape(())) if single else (out, cost)
 
     def set_candidate_refine(self, n_steps: int, pos_tol: float = mm_to_m(1), rot_tol: float = 0.1):
         """Levenberg-Marquardt steps on EVERY candidate of generate_ranked_ik_solutions, generate_diverse_ik_solutions and generate_ik_path,
@@ -738,6 +832,7 @@ class IKFlowSolver:
             path, index, cost, reach, nodes = eng.generate_path(waypoints, k, latent, shared_latent, clamp_to_joint_limits, opt,
                                                                 q_start=q_start, node_costs=return_node_costs)
             cost = cost.reshape(())
+            self._last_path_opt_paths = 1 if (self._path_optimization[0] and T > 0) else None
             if refine_steps > 0 and T > 0 and bool(torch.isfinite(cost).item()):
                 for _ in range(refine_steps):
                     path = eng.lm_step(waypoints, path)
@@ -799,6 +894,7 @@ class IKFlowSolver:
                                    min_clearance, node_weight, max_joint_step)
             paths, index, cost, reach, nodes = eng.generate_paths(waypoints, k, latent, shared_latent, clamp_to_joint_limits, opt,
                                                                   q_start=q_start, node_costs=return_node_costs)
+            self._last_path_opt_paths = P if (self._path_optimization[0] and n > 0) else None
             if refine_steps > 0 and n > 0:
                 found = torch.isfinite(cost)
                 if bool(found.any().item()):   # only the paths that exist: a no-path entry stays at zeros
